@@ -10,13 +10,20 @@ before the timed region), so no step re-reads the previous step's targets or row
 the whole 100M-node table and a step answers 8M queries. No data-path collective (owner
 routing).
 
-The same line carries the north-star variant as `allgather` (the 100M-node
-table split over the N GPUs without halo, 1M global queries per step replicated on every rank,
-RCCL all-gather of rows and parts + device merge), the status-refresh cost (`refresh`), and
-two CPU baselines timed on the host cores (`cpu_baseline`: the structure-faithful port of the
-reference's std::list walk, and `fast_cpu`: the closed-form binary-search window on all cores).
+A plain run does only that: set up, warm up, time the K steps, print the line. More than 128
+steps rotate over 128 batches (27 times the Infinity Cache), and more than 2048 go out as replays
+of one HIP graph of 2048 launches. --dump-outputs DIR writes the last timed step's rows and counts
+as DIR/idx.npy and DIR/cnt.npy (dump_outputs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+With --full the same line carries the check of the last step's rows against the CPU restatement
+(`verified`), the north-star variant as `allgather` (the 100M-node
+table split over the N GPUs without halo, 1M global queries per step replicated on every rank,
+RCCL all-gather of rows and parts + device merge), the status-refresh cost (`refresh`), the other
+passes of DESIGN.md §5.1, and two CPU baselines timed on the host cores (`cpu_baseline`: the
+structure-faithful port of the reference's std::list walk, and `fast_cpu`: the closed-form
+binary-search window on all cores).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N ranks itself (one
@@ -38,8 +45,12 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 METRIC = "k=8 closest-node queries/sec at 100M-node table (1/8 GPU) + % HBM roofline"
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (AMD's data sheet: 8 TB/s)
 LINE_BYTES = {8: 128, 16: 128, 32: 256}  # window line gathered per query
+MAX_BATCHES = 128  # default cap on the rotated batches (54 MB each; 128 of them are 27 times the Infinity Cache)
+GRAPH_STEPS = 2048  # longest HIP graph: more steps go out as replays of one graph of up to this many launches
+DUMP_BYTES = 40_000_000  # --dump-outputs: most it writes per rank (float64 indices, float32 counts: 8 k + 4 bytes per row)
+DUMP_SEED = 0x0D470D0  # of the row sample, when a step returns more than that
 
 
 def parse_args(argv=None):
@@ -50,7 +61,16 @@ def parse_args(argv=None):
     ap.add_argument("--count", type=int, default=8)
     ap.add_argument("--queries", type=int, default=1 << 20, help="queries per GPU per step")
     ap.add_argument("--batches", type=int, default=0,
-                    help="distinct target batches rotated over the steps (0: one per step, warm-up included)")
+                    help=f"distinct target batches rotated over the steps (0: one per step, warm-up included, at most "
+                         f"{MAX_BATCHES})")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the check of the last step's rows against the CPU restatement, the "
+                         "reference-structure bytes, the CPU baselines, the cold-cache / refresh / host-buffer / "
+                         "other-count / latency / config passes, the owner-routed step and the north-star variant "
+                         "(--no-cpu, --no-extras, --no-allgather, --no-rccl1 leave parts of it out)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (its rows and counts; a fixed seeded sample of the "
+                         f"rows where they would exceed {DUMP_BYTES // 10**6} MB) as DIR/<name>.npy")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of port CPU baseline sampling")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
@@ -293,6 +313,23 @@ def load_json(path, key=None):
     return d.get(key) if key else d
 
 
+def dump_outputs(path, idx, cnt, world=1, rank=0):
+    """--dump-outputs: what the last timed step returned to its caller, as path/idx.npy (the rows: global node
+    indices, -1 where a row has fewer, float64 so that every index is exact) and path/cnt.npy (the rows' counts,
+    float32); at N > 1 every rank writes its own pair, named idx_rank<r> / cnt_rank<r>. A step returning more than
+    DUMP_BYTES has a fixed sample of its rows written (the same rows in every run: DUMP_SEED, in ascending order)."""
+    n = idx.shape[0]
+    keep = DUMP_BYTES // (8 * idx.shape[1] + 4)
+    tag = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    i, c = idx.cpu().numpy(), cnt.cpu().numpy()
+    if n > keep:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+        i, c = i[rows], c[rows]
+    np.save(os.path.join(path, f"idx{tag}.npy"), i.astype(np.float64))
+    np.save(os.path.join(path, f"cnt{tag}.npy"), c.astype(np.float32))
+
+
 # ---------------------------------------------------------------------------------------------
 # owner routing (the headline)
 # ---------------------------------------------------------------------------------------------
@@ -318,7 +355,9 @@ def main_owner(args):
     sh = build_shard(spec, rank)
     T = DeviceTable(sh.ids, sh.status, sh.first, sh.off, device=local, index_base=sh.index_base, sorted=True)
     Q, K, W, cnt_k = args.queries, args.steps, args.warmup, args.count
-    NB = args.batches or (K + W)
+    if K < 1 or W < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    NB = args.batches or min(K + W, MAX_BATCHES)
     tgs = device_targets(NB, Q, spec.shard_bits, rank, 0x0D470002 + 7919 * rank, dev)
     outs = [torch.empty((Q, cnt_k), dtype=torch.int32, device=dev) for _ in range(NB)]
     ocnt = [torch.empty((Q,), dtype=torch.uint8, device=dev) for _ in range(NB)]
@@ -340,36 +379,45 @@ def main_owner(args):
     torch.cuda.synchronize(dev)
 
     # The K steps go out as one HIP graph of K launches (a step is ~30 us; issuing them one by one
-    # from Python leaves ~3 us gaps). Step j reads batch j and writes output j. --no-graph issues
-    # them one by one with an event per step.
+    # from Python leaves ~3 us gaps). Step j reads batch j % NB and writes output j % NB. More than GRAPH_STEPS
+    # steps go out as replays of one graph of C launches (C a multiple of NB, so every replay starts at batch 0)
+    # and one graph of the K % C steps left. --no-graph issues them one by one with an event per step.
+    C = K if K <= GRAPH_STEPS else NB * max(1, GRAPH_STEPS // NB)
     graph = None
     if not args.no_graph:
         try:
-            g = torch.cuda.CUDAGraph()
+            graph = []  # (graph, replays)
             cs = torch.cuda.Stream(dev)
-            cs.wait_stream(stream)
-            with torch.cuda.graph(g, stream=cs):
-                for j in range(K):
-                    step(j, cs.cuda_stream)
-            stream.wait_stream(cs)
-            torch.cuda.synchronize(dev)
-            graph = g
+            for j0, n, replays in ((0, C, K // C), (K - K % C, K % C, 1)):
+                if n == 0:
+                    continue
+                g = torch.cuda.CUDAGraph()
+                cs.wait_stream(stream)
+                with torch.cuda.graph(g, stream=cs):
+                    for j in range(j0, j0 + n):
+                        step(j, cs.cuda_stream)
+                stream.wait_stream(cs)
+                torch.cuda.synchronize(dev)
+                graph.append((g, replays))
         except Exception as e:  # capture unsupported: fall back to eager launches
             print(f"graph capture failed ({e}); eager launches", file=sys.stderr)
             graph = None
-    if graph is not None:  # the graph's first launch uploads it: run it once untimed over the warm-up
-        graph.replay()
+    if graph is not None:  # a graph's first launch uploads it: run each once untimed over the warm-up
+        for g, _ in graph:
+            g.replay()
         for j in range(W):
             step(K + j, stream.cuda_stream)
         torch.cuda.synchronize(dev)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(K + 1)]
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 if graph is not None else K + 1)]
     if dist:
         dist.barrier()
     torch.cuda.synchronize(dev)
     t_start = time.perf_counter()
     ev[0].record(stream)
     if graph is not None:
-        graph.replay()
+        for g, replays in graph:
+            for _ in range(replays):
+                g.replay()
         ev[-1].record(stream)
     else:
         for j in range(K):
@@ -385,15 +433,26 @@ def main_owner(args):
         kern_ms = [ev[j].elapsed_time(ev[j + 1]) for j in range(K)]
     t_max = max_over_ranks(dist, wall, dev)
     avg_kernel_s = float(np.mean(kern_ms)) / 1e3
+    if args.dump_outputs:  # (before the passes below, which reuse the buffers)
+        dump_outputs(args.dump_outputs, outs[(K - 1) % NB], ocnt[(K - 1) % NB], world, rank)
 
     # bytes the timed kernel must move per query: the target, its ONE window line, the row and count
     moved_q = 20 + line_b + 4 * cnt_k + 1
     achieved = moved_q * Q / avg_kernel_s / 1e9
-    # SURVEY §8(d)'s reference-structure bytes (IDs of every good node of W(R), status bytes, extents)
+    # --full: SURVEY §8(d)'s reference-structure bytes (IDs of every good node of W(R), status bytes, extents)
     # over the first batches, exact on the host; reported without a fraction (the layout reads less)
-    ref = [rt_algorithmic_bytes(sh.status, sh.off, T.find_bucket(tgs[j]).cpu().numpy().view(np.uint32)
-                                .astype(np.int64), cnt_k) for j in range(min(4, NB))]
-    ref_bytes = float(np.mean([r[0] for r in ref]))
+    ref_structure = None
+    if args.full:
+        ref = [rt_algorithmic_bytes(sh.status, sh.off, T.find_bucket(tgs[j]).cpu().numpy().view(np.uint32)
+                                    .astype(np.int64), cnt_k) for j in range(min(4, NB))]
+        ref_structure = {
+            "bytes_per_query": float(np.mean([r[0] for r in ref])) / Q,
+            "basis": "SURVEY.md §8(d): 20 + sum over W(R) of (8 + n_b + 20 g_b) + 4k, the bytes the "
+                     "reference's own data structure must read (no fraction: the window lines read less)",
+            "window_means": {"buckets": float(np.mean([r[1] for r in ref])),
+                             "nodes": float(np.mean([r[2] for r in ref])),
+                             "good": float(np.mean([r[3] for r in ref]))},
+        }
     traffic = traffic_src = None
     tj = load_json(args.traffic_json)
     if tj and tj.get("kernel", "") in kernel and tj.get("count") == cnt_k:
@@ -415,18 +474,20 @@ def main_owner(args):
                     "table_MB": int(row.split("MB")[0]), "line_bytes": line_b,
                     "us_per_1M_rotated": a[row]["us_per_1M"], "us_per_1M_cold": a[row + "_cold"]["us_per_1M"]}
 
-    # the rows of the last timed step (batch K-1; before the extras, which reuse the buffers and change the
+    # --full: the rows of the last timed step (batch K-1; before the extras, which reuse the buffers and change the
     # status), checked against the CPU restatement on this rank's
     # shard table (exact halo: every owned window lies inside it)
-    vrows = min(Q, args.verify_rows)
-    vt = tgs[(K - 1) % NB][:vrows].cpu().numpy()
-    bad = verify_rows(sh.ids, sh.status, sh.first, sh.off, sh.index_base, vt,
-                      outs[(K - 1) % NB][:vrows].cpu().numpy(), ocnt[(K - 1) % NB][:vrows].cpu().numpy(), cnt_k)
-    verified = {"rows": sum_over_ranks(dist, vrows), "mismatches": sum_over_ranks(dist, bad),
-                "what": f"the first {vrows} rows (indices, counts) of every rank's last timed step, against the "
-                        "closed-form CPU restatement (oracle/) on the rank's shard table"}
+    verified = None
+    if args.full:
+        vrows = min(Q, args.verify_rows)
+        vt = tgs[(K - 1) % NB][:vrows].cpu().numpy()
+        bad = verify_rows(sh.ids, sh.status, sh.first, sh.off, sh.index_base, vt,
+                          outs[(K - 1) % NB][:vrows].cpu().numpy(), ocnt[(K - 1) % NB][:vrows].cpu().numpy(), cnt_k)
+        verified = {"rows": sum_over_ranks(dist, vrows), "mismatches": sum_over_ranks(dist, bad),
+                    "what": f"the first {vrows} rows (indices, counts) of every rank's last timed step, against the "
+                            "closed-form CPU restatement (oracle/) on the rank's shard table"}
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         extras["cold"] = cold_pass(T, tgs, outs, ocnt, cnt_k, Q, moved_q, dev, stream)
         # (before refresh_pass, which moves `now` and so the statuses the rows are checked against)
         # N > 1: in child processes whose data path runs on an RCCL group (owner_child); N = 1: no exchange here,
@@ -446,11 +507,11 @@ def main_owner(args):
         if rank == 0 and world == 1:
             extras["configs"] = configs_pass(dev)
     cpu = fast = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         host_t = tgs[0][:1 << 17].cpu().numpy()
         cpu, fast = cpu_baselines(sh, host_t, cnt_k, args.cpu_budget, all_cores())
     ag = None
-    if not args.no_extras and not args.no_allgather:
+    if args.full and not args.no_extras and not args.no_allgather:
         T.close()
         del tgs, outs, ocnt
         torch.cuda.empty_cache()
@@ -475,13 +536,15 @@ def main_owner(args):
             "steps": K,
             "warmup": W,
             "ms_per_step": t_max / K * 1e3,
+            "full": bool(args.full),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "u64",
             "data": "synthetic (SURVEY.md §8d recipe: 100M mt19937_64 IDs, seed 0x0D470001, status 80/10/10 "
                     "good/expired/dubious from seed 0x0D470003, U(24) buckets; uniform targets, "
-                    f"{NB} distinct batches of {Q} per GPU, one per step)",
+                    f"{NB} distinct batches of {Q} per GPU, "
+                    f"{'one per step' if NB >= K + W else 'rotated over the steps'})",
             "config": {
                 "workload": "config3: 100M-node U(24) routing table, 1/8 shard per GPU (2^21 owned buckets "
                             f"+ halo, {sh.ids.shape[0]} nodes on rank 0), {Q} owned queries per GPU "
@@ -505,18 +568,12 @@ def main_owner(args):
                 "bytes_basis": f"bytes the kernel must move per query: 20 target + {line_b} window line "
                                f"+ {4 * cnt_k} row + 1 count (the 128-byte fallback lines and exact-path reads of "
                                "the rare queries that need them not counted)",
-                "launch": "hip graph of K launches" if graph is not None else "K eager launches",
+                "launch": ("K eager launches" if graph is None else "hip graph of K launches" if C == K
+                           else f"replays of a hip graph of {C} launches"),
                 "avg_kernel_ms": avg_kernel_s * 1e3,
                 "random_line_ceiling": ceil,
                 "frac_of_ceiling": (ceil["us_per_1M_rotated"] * Q / 2**20 / 1e3 / (avg_kernel_s * 1e3)) if ceil else None,
-                "alg_bytes_ref_structure": {
-                    "bytes_per_query": ref_bytes / Q,
-                    "basis": "SURVEY.md §8(d): 20 + sum over W(R) of (8 + n_b + 20 g_b) + 4k, the bytes the "
-                             "reference's own data structure must read (no fraction: the window lines read less)",
-                    "window_means": {"buckets": float(np.mean([r[1] for r in ref])),
-                                     "nodes": float(np.mean([r[2] for r in ref])),
-                                     "good": float(np.mean([r[3] for r in ref]))},
-                },
+                "alg_bytes_ref_structure": ref_structure,
             },
             "verified": verified,
             "cpu_baseline": cpu,
