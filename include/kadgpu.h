@@ -328,6 +328,36 @@ int kad_rt_closest_batch_dual(const kad_table* table4, const kad_table* table6,
                               const uint8_t* targets, const uint8_t* af, uint32_t q, uint32_t count,
                               uint32_t* out_idx, uint8_t* out_cnt, void* stream);
 
+/* ---- storage responsibility (Dht::maintainStorage dht.cpp:2909-2937, Dht::onAnnounce dht.cpp:3352-3358) ---- */
+/* Both call sites take findClosestNodes(h, now, count) and use one bit of it: h.xorCmp(nodes.back()->id, myid) < 0,
+ * "the last returned node is closer to h than we are". Batched, per target h, on the table's status snapshot:
+ *   R = findClosestNodes(h, now, count) (the window semantics of kad_rt_closest_batch), n = |R|
+ *   far = n >= max(min_nodes, 1) && xorCmp_h(id(R[n-1]), self_id) < 0     (strict 160-bit compare; a last node
+ *         equal to self_id is not far; an empty table, no good node or count == 0: not far)
+ * maintainStorage: count = KAD_TARGET_NODES, min_nodes = 1 (dht.cpp:2909-2926); onAnnounce: count =
+ * KAD_SEARCH_NODES, min_nodes = KAD_TARGET_NODES (dht.cpp:3352-3358).
+ * self_id: 20 host bytes; targets: device, q x 20 bytes; out_far: device, q bytes, 0 or KAD_RESP_FAR. One byte per
+ * query leaves instead of a 33-byte row. Enqueues on `stream` and does not synchronise. A const query without
+ * table-held scratch: concurrent calls on distinct streams are safe. count <= 8 on tables with short window lines
+ * or slot lines answers from one line per query; every other shape, and counts 9..KAD_MAX_COUNT, one wave per
+ * query. Checked in this order, before the table is read or any device work: NULL table, NULL self_id / targets /
+ * out_far (KAD_ERR_INVALID); q == 0 (KAD_OK); count > KAD_MAX_COUNT (KAD_ERR_UNSUPPORTED). */
+#define KAD_RESP_FAR 1u
+#define KAD_RESP_FAR4 1u
+#define KAD_RESP_FAR6 2u
+int kad_rt_responsible_batch(const kad_table* t, const uint8_t* self_id, const uint8_t* targets, uint32_t q,
+                             uint32_t count, uint32_t min_nodes, uint8_t* out_far, void* stream);
+/* Both families answer every target, as maintainStorage asks both (dht.cpp:2909-2926): out[i] = KAD_RESP_FAR4 if far
+ * in table4 | KAD_RESP_FAR6 if far in table6, one launch. A NULL family behaves as an empty table (its bit is 0);
+ * both NULL, or tables on different devices: KAD_ERR_INVALID. out[i] == 3 is maintainStorage's "discard". */
+int kad_rt_responsible_batch_dual(const kad_table* table4, const kad_table* table6, const uint8_t* self_id,
+                                  const uint8_t* targets, uint32_t q, uint32_t count, uint32_t min_nodes,
+                                  uint8_t* out, void* stream);
+/* kad_rt_responsible_batch on host buffers, synchronous, ordered after every change made to the table before the
+ * call; device buffers and a stream of the call's own. */
+int kad_rt_responsible_batch_host(const kad_table* t, const uint8_t* self_id, const uint8_t* targets, uint32_t q,
+                                  uint32_t count, uint32_t min_nodes, uint8_t* out_far);
+
 /* Per-query family select for NodeCache::getCachedNodes(id, sa_family, count) (node_cache.cpp:36-66:
  * cache_4 or cache_6 by family; Dht::refill asks the search's family, dht.cpp:1650): af[i] = 0 -> table4,
  * 1 -> table6 (KAD_TABLE_SORTED tables; either may be NULL = an empty map). Any count (as kad_nc_closest_batch).

@@ -110,6 +110,15 @@ public:
                      "kad_nc_closest_batch_host");
     }
 
+    /* Storage-responsibility verdicts on host buffers (kad_rt_responsible_batch_host): one byte per target. */
+    void responsibleBatch(const uint8_t* self_id, const uint8_t* targets, size_t q, size_t count, size_t min_nodes,
+                          std::vector<uint8_t>& far) const {
+        far.resize(q);
+        if (q) check(kad_rt_responsible_batch_host(t_, self_id, targets, (uint32_t)q, (uint32_t)count,
+                                                   (uint32_t)min_nodes, far.data()),
+                     "kad_rt_responsible_batch_host");
+    }
+
     /* Node liveness (kad_table_set_times / kad_table_patch_times) and the device-side isGood(now)
      * refresh (kad_table_refresh_status, incremental). */
     void setTimes(const std::vector<int64_t>& time_ns, const std::vector<int64_t>& reply_ns,
@@ -235,6 +244,52 @@ public:
     std::vector<std::vector<NodePtr>> findClosestNodesBatch(const std::vector<InfoHashT>& ids, TimePoint now,
                                                             size_t count = KAD_TARGET_NODES) const {
         return findClosestNodesBatch(ids.data(), ids.size(), now, count);
+    }
+
+    /* The storage-responsibility question of Dht::maintainStorage (dht.cpp:2909-2937: count = TARGET_NODES,
+     * min_nodes = 1) and Dht::onAnnounce (dht.cpp:3352-3358: count = SEARCH_NODES, min_nodes = TARGET_NODES), per id:
+     * 1 when findClosestNodes(id, now, count) returns at least max(min_nodes, 1) nodes and
+     * id.xorCmp(nodes.back()->id, myid) < 0 (the last of them is closer to id than we are), else 0. A few requests
+     * take the host path (findClosestNodesHost and a host xor compare), batches kad_rt_responsible_batch_host:
+     * one byte per id comes back instead of a row. */
+    template <class InfoHashT, class TimePoint>
+    std::vector<uint8_t> isTooFarBatch(const InfoHashT* ids, size_t q, const InfoHashT& myid, TimePoint now,
+                                       size_t count = KAD_TARGET_NODES, size_t min_nodes = 1) const {
+        std::vector<uint8_t> out(q, 0);
+        const size_t need = std::max<size_t>(min_nodes, 1);
+        auto far_of = [&](const InfoHashT& id, const std::vector<NodePtr>& r) -> uint8_t {
+            if (r.size() < need) return 0;
+            const uint8_t* t = id_bytes(id);
+            const uint8_t* a = id_bytes(r.back()->id);
+            const uint8_t* me = id_bytes(myid);
+            for (unsigned k = 0; k < KAD_HASH_LEN; k++) {  // InfoHash::xorCmp (infohash.h:131-146)
+                const uint8_t da = a[k] ^ t[k], dm = me[k] ^ t[k];
+                if (da != dm) return da < dm ? (uint8_t)KAD_RESP_FAR : (uint8_t)0;
+            }
+            return 0;
+        };
+        if (q <= hostBatchLimit() && count <= host_count_) {
+            for (size_t i = 0; i < q; i++) out[i] = far_of(ids[i], findClosestNodesHost(ids[i], now, count));
+            return out;
+        }
+        if (std::min(count, nodes_.size()) > KAD_MAX_COUNT) {  // any size_t count: rows, then the compare here
+            const std::vector<std::vector<NodePtr>> r = findClosestNodesBatch(ids, q, now, count);
+            for (size_t i = 0; i < q; i++) out[i] = far_of(ids[i], r[i]);
+            return out;
+        }
+        advance(to_ns(now));
+        count = std::min(count, nodes_.size());
+        if (count == 0 || q == 0) return out;
+        if (count < need) return out;  // fewer nodes than min_nodes can ever come back
+        std::vector<uint8_t> targets(q * KAD_HASH_LEN);
+        for (size_t i = 0; i < q; i++) std::memcpy(&targets[i * KAD_HASH_LEN], id_bytes(ids[i]), KAD_HASH_LEN);
+        table_.responsibleBatch(id_bytes(myid), targets.data(), q, count, min_nodes, out);
+        return out;
+    }
+    template <class InfoHashT, class TimePoint>
+    std::vector<uint8_t> isTooFarBatch(const std::vector<InfoHashT>& ids, const InfoHashT& myid, TimePoint now,
+                                       size_t count = KAD_TARGET_NODES, size_t min_nodes = 1) const {
+        return isTooFarBatch(ids.data(), ids.size(), myid, now, count, min_nodes);
     }
 
     /* A mirrored node's time / reply_time / expired_ changed (Node::received, setExpired, reset,
@@ -647,6 +702,19 @@ public:
     template <class InfoHashT>
     std::vector<NodePtr> findClosestNodes(const InfoHashT& id, sa_family_t af, size_t count = KAD_TARGET_NODES) const {
         return buckets(af).findClosestNodes(id, clock_(), count);
+    }
+    /* Dht::maintainStorage's verdict for every stored key in one pass (dht.cpp:2909-2937): byte i = KAD_RESP_FAR4
+     * if keys[i] is too far in the IPv4 table | KAD_RESP_FAR6 if in the IPv6 table (count = TARGET_NODES, any result
+     * counts); 3 is the reference's "discard". One isTooFarBatch per family, host buffers (device-pointer callers
+     * get both bits from one launch, kad_rt_responsible_batch_dual). */
+    template <class InfoHashT>
+    std::vector<uint8_t> maintainStorageBatch(const std::vector<InfoHashT>& keys, const InfoHashT& myid,
+                                              time_point now) const {
+        const std::vector<uint8_t> a = v4_.isTooFarBatch(keys, myid, now), b = v6_.isTooFarBatch(keys, myid, now);
+        std::vector<uint8_t> out(keys.size());
+        for (size_t i = 0; i < out.size(); i++)
+            out[i] = (uint8_t)((a[i] ? KAD_RESP_FAR4 : 0u) | (b[i] ? KAD_RESP_FAR6 : 0u));
+        return out;
     }
     /* Dht::buckets(af) (dht.h:437-438) */
     const RoutingTableMirror<RoutingTableT>& buckets(sa_family_t af) const { return af == AF_INET ? v4_ : v6_; }

@@ -35,6 +35,7 @@ KAD_INFO_NODECACHE_LINES32 = 0x1000
 KAD_INFO_SLOT_LINES = 0x2000
 KAD_SERVE_MAX_Q, KAD_SERVE_MAX_COUNT, KAD_SERVE_MAX_IDLE_US = 64, 64, 1000000
 KAD_OP_REMOVE, KAD_OP_REPLACE, KAD_OP_INSERT, KAD_OP_SPLIT = 1, 2, 3, 4
+KAD_RESP_FAR, KAD_RESP_FAR4, KAD_RESP_FAR6 = 1, 1, 2
 
 
 def row_words(count: int) -> int:
@@ -79,6 +80,7 @@ def shard_block_words(count: int, row_cap: int, part_cap: int) -> int:
             + KAD_SHARD_COUNTERS * KAD_SHARD_COUNTER_STRIDE)
 
 
+KAD_ERR_INVALID = -1
 KAD_ERR_NOMEM = -3
 KAD_ERR_UNSUPPORTED = -4
 
@@ -125,6 +127,9 @@ SIGNATURES = {
     "kad_nc_closest_batch_host": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
     "kad_rt_closest_batch_dual": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "kad_nc_closest_batch_dual": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    "kad_rt_responsible_batch": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
+    "kad_rt_responsible_batch_dual": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
+    "kad_rt_responsible_batch_host": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P]),
     "kad_rt_shard_batch": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
                                      _P, _P]),

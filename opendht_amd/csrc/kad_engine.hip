@@ -2530,6 +2530,201 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     rt_sl_kernel_body<ABL, true>(T, targets, q, count, out_idx, out_cnt);
 }
 
+// ---------------------------------------------------------------------------------------
+// Storage-responsibility verdicts (kad_rt_responsible_batch): Dht::maintainStorage (dht.cpp:2909-2937) and
+// Dht::onAnnounce (dht.cpp:3352-3358) take findClosestNodes(h, now, count) and ask one question of it:
+// h.xorCmp(nodes.back()->id, myid) < 0, "is the last returned node closer to h than we are". One byte per query
+// leaves instead of a 33-byte row: the answer stays in registers (count <= 8 on tables with short window lines or
+// slot lines) or in a per-wave LDS row (every other shape and count), and an epilogue compares its last node with
+// self_id.
+//
+// The epilogue's load of key[last] is a second dependent random request, about the cost of the line itself, so
+// it is skipped where the line already decides. A line answers only targets inside its bucket's range, and every
+// node it returns lies in the window's ID range, so target and nodes share that range's common prefix of P bits
+// (short lines: buckets b-3 .. b+2 of depth d, clipped to the table, P = d - bitlen(prefix_lo ^ prefix_hi); slot
+// lines: the line's cp). If self_id differs from the target within those P bits, self's XOR distance has a one
+// where the last node's has zeros: far, whichever node is last. Every other case (self_id inside the window's
+// prefix, answers from the 128-byte lines or the exact path) loads the key; a tie of the top 64 distance bits loads
+// the target's low 96 bits and the node's tail and finishes the 160-bit compare.
+// MODE (KAD_ABLATIONS tools build only): 1 = no line-decided verdicts (every query loads), 2 = statistics, bit 7 of
+// the byte marks a line-decided verdict.
+// ---------------------------------------------------------------------------------------
+
+// xorCmp_h(id(last), self) < 0 (infohash.h:131-146); last carries index_base; thi = the target's top 64 bits.
+__device__ __forceinline__ uint32_t resp_compare(const DevTable& T, uint32_t last, uint64_t thi,
+                                                 const uint8_t* __restrict__ targets, uint32_t i, const Target& self) {
+    const uint32_t j = last - T.index_base;
+    const uint64_t a = T.key[j] ^ thi, s = self.hi ^ thi;
+    if (a != s) return a < s ? 1u : 0u;
+    const Target t = load_target(targets, i);
+    const uint32_t* tl = T.tail + 3ull * j;
+    return cmp160(0, tl[0] ^ t.t2, tl[1] ^ t.t3, tl[2] ^ t.t4, 0, self.t2 ^ t.t2, self.t3 ^ t.t3, self.t4 ^ t.t4) < 0
+               ? 1u : 0u;
+}
+
+// o[k], k < 8, as a chain of selects: left to itself the compiler turns the chain back into o[k], an array in
+// scratch memory and a dependent load on every query (the empty asm keeps each step opaque).
+__device__ __forceinline__ uint32_t pick8(const uint32_t (&o)[8], uint32_t k) {
+    uint32_t v = o[0];
+#pragma unroll
+    for (int j = 1; j < 8; j++) {
+        v = k == (uint32_t)j ? o[j] : v;
+        asm volatile("" : "+v"(v));
+    }
+    return v;
+}
+
+// One table's verdict for the lane's query, count <= 8 (0 or 1; bit 7 with MODE 2). Lines where the table has them,
+// the wave-cooperative exact path (wave_exact into the wave's LDS row) for whatever is left, which on a table
+// without short or slot lines is every query. need_n = max(min_nodes, 1). Call from wave-uniform control flow.
+template <int MODE>
+__device__ __forceinline__ uint32_t resp_lines(const DevTable& T, const uint8_t* __restrict__ targets, uint32_t i,
+                                               bool act, uint64_t thi, uint32_t count, uint32_t need_n,
+                                               const Target& self, uint64_t* xs, uint32_t* xrow, uint8_t* xcnt) {
+    if (T.B == 0 || count == 0) return 0u;  // kernel-uniform: an empty table answers nothing (routing_table.cpp:73)
+    bool have = false, decided = false, need = act;
+    uint32_t mm = 0, last = NONE;
+    if (T.flags & TF_WS) {
+        Target t{};
+        uint32_t b = 0;
+        if (act) {
+            t.hi = thi;
+            b = locate_bucket(T, t);
+        }
+        uint32_t o[8], m;
+        const bool ok = ws_answer<0>(T, t, b, count, act, o, m) && act;
+        if (ok) {
+            have = true;
+            mm = m;
+            last = m ? pick8(o, m - 1) : NONE;
+            if (MODE != 1) {
+                const uint64_t pre0 = T.rbase >> T.rshift;
+                const uint64_t x = (pre0 + (b > 3u ? b - 3u : 0u)) ^ (pre0 + min(b + 2u, T.B - 1u));
+                const uint32_t bl = x ? 64u - (uint32_t)__builtin_clzll(x) : 0u;
+                decided = (((self.hi ^ thi) >> T.rshift) >> bl) != 0;
+            }
+        }
+        need = act && !ok;
+        if (__any(need)) {  // the 128-byte line of the (few) queries the short line cannot answer
+            const bool ok2 = wl_answer<0>(T, t, b, count, need, o, m);
+            if (need && ok2) {
+                have = true;
+                mm = m;
+                last = m ? pick8(o, m - 1) : NONE;
+            }
+            need = need && !ok2;
+        }
+    } else if (T.flags & TF_SL) {
+        const bool in = act && thi >= T.rbase && ((thi - T.rbase) >> T.slshift) < T.slslots;
+        const uint32_t j = in ? (uint32_t)((thi - T.rbase) >> T.slshift) : 0u;
+        uint32_t o[8], m, bh;
+        const bool ok = sl_answer(T, thi, j, count, in, o, m, bh) && in;
+        if (ok) {
+            have = true;
+            mm = m;
+            last = m ? pick8(o, m - 1) : NONE;
+            if (MODE != 1) {
+                const uint32_t cp = T.sl[4ull * j].z & 63u;  // the line's dw2, still in registers
+                decided = cp && ((self.hi ^ thi) >> (64u - cp)) != 0;
+            }
+        }
+        need = act && !ok;
+        if (__any(need)) {  // locate and the 128-byte line (the full target: the locate may compare the low bits)
+            Target t{};
+            uint32_t b = 0;
+            if (need) {
+                t = load_target(targets, i);
+                b = bh != NONE ? bh : locate_bucket(T, t);
+            }
+            const bool ok2 = gl_answer(T, t, b, count, need, o, m);
+            if (need && ok2) {
+                have = true;
+                mm = m;
+                last = m ? pick8(o, m - 1) : NONE;
+            }
+            need = need && !ok2;
+        }
+    }
+    if (__any(need)) {  // the exact path, one query at a time by the wave, its row in LDS
+        const uint32_t lane = threadIdx.x & 63u;
+        Target t{};
+        if (need) t = load_target(targets, i);
+        for (uint64_t mk = __ballot(need); mk; mk &= mk - 1) {
+            const uint32_t l = (uint32_t)__builtin_ctzll(mk);
+            Target u;
+            u.hi = rdl64(t.hi, l);
+            u.t2 = rdl(t.t2, l);
+            u.t3 = rdl(t.t3, l);
+            u.t4 = rdl(t.t4, l);
+            wave_exact(T, u, count, xrow, xcnt, xs);
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            if (lane == l) {
+                have = true;
+                mm = *xcnt;
+                last = mm ? xrow[mm - 1] : NONE;
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    if (!have || mm < need_n) return 0u;
+    if (decided) return MODE == 2 ? 0x81u : 1u;
+    return resp_compare(T, last, thi, targets, i, self);
+}
+
+// count <= 8, one lane per query; DUAL: both families answer every query (bit 0 = T4, bit 1 = T6), one after the
+// other. 8 waves per SIMD as rt_ws_kernel: the gathers are latency-bound.
+template <int MODE, bool DUAL>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void resp_line_kernel(
+    DevTable T4, DevTable T6, uint64_t shi, uint32_t s2, uint32_t s3, uint32_t s4, const uint8_t* __restrict__ targets,
+    uint32_t q, uint32_t count, uint32_t need_n, uint8_t* __restrict__ out) {
+    __shared__ uint64_t xs[BLOCK / 64][192];
+    __shared__ uint32_t xrow[BLOCK / 64][8];
+    __shared__ uint8_t xcnt[BLOCK / 64];
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x, w = threadIdx.x >> 6;
+    const bool act = i < q;
+    const Target self{shi, s2, s3, s4};
+    const uint64_t thi = act ? load_target_hi(targets, i) : 0ull;
+    uint32_t far = resp_lines<MODE>(T4, targets, i, act, thi, count, need_n, self, xs[w], xrow[w], &xcnt[w]);
+    if (DUAL) far |= resp_lines<MODE>(T6, targets, i, act, thi, count, need_n, self, xs[w], xrow[w], &xcnt[w]) << 1;
+    if (act) out[i] = (uint8_t)far;
+}
+
+// One table's verdict for a wave-uniform target, any shape, count <= KAD_MAX_COUNT: the window and its ranking by
+// the wave (wave_window + wave_rank, as wave_exact) into the wave's LDS row.
+__device__ __forceinline__ uint32_t resp_wave_one(const DevTable& T, const Target& t, const uint8_t* __restrict__ targets,
+                                                  uint32_t i, uint32_t count, uint32_t need_n, const Target& self,
+                                                  uint64_t* xs, uint32_t* xrow, uint8_t* xcnt) {
+    if (T.B == 0 || count == 0) return 0u;
+    wave_exact(T, t, count, xrow, xcnt, xs);
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t m = *xcnt;
+    const uint32_t last = m ? xrow[m - 1] : NONE;
+    __builtin_amdgcn_wave_barrier();  // the row is reused by the wave's next table
+    if (m < need_n) return 0u;
+    return resp_compare(T, last, t.hi, targets, i, self);
+}
+
+// The general path: one wave per query (as rt_wave_kernel), both families one after the other when `dual`.
+__global__ __launch_bounds__(BLOCK) void resp_wave_kernel(DevTable T4, DevTable T6, uint32_t dual, uint64_t shi,
+                                                          uint32_t s2, uint32_t s3, uint32_t s4,
+                                                          const uint8_t* __restrict__ targets, uint32_t q, uint32_t count,
+                                                          uint32_t need_n, uint8_t* __restrict__ out) {
+    __shared__ uint64_t xs[BLOCK / 64][192];
+    __shared__ uint32_t xrow[BLOCK / 64][KAD_MAX_COUNT];
+    __shared__ uint8_t xcnt[BLOCK / 64];
+    const uint32_t w = threadIdx.x >> 6, i = blockIdx.x * (BLOCK / 64) + w;
+    if (i >= q) return;  // wave-uniform
+    const Target self{shi, s2, s3, s4};
+    const Target t = load_target(targets, i);
+    uint32_t far = resp_wave_one(T4, t, targets, i, count, need_n, self, xs[w], xrow[w], &xcnt[w]);
+    if (dual) far |= resp_wave_one(T6, t, targets, i, count, need_n, self, xs[w], xrow[w], &xcnt[w]) << 1;
+    if ((threadIdx.x & 63u) == 0) out[i] = (uint8_t)far;
+}
+
 // Fallback slot lines (dw1 == NONE) and those without a bucket (dw0 == NONE): cnt[0], cnt[1] (KAD_DEBUG).
 __global__ void sl_count_kernel(const uint32_t* sl, uint32_t slslots, uint32_t* cnt) {
     const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
@@ -9445,6 +9640,113 @@ int kad_rt_closest_batch_dual(const kad_table* t4, const kad_table* t6, const ui
     else launch_rt_dual<32>(d4, d6, targets, af, q, count, out_idx, out_cnt, s);
     HIP_TRY(hipGetLastError());
     return KAD_OK;
+}
+
+// Storage-responsibility verdicts (Dht::maintainStorage dht.cpp:2909-2937, Dht::onAnnounce dht.cpp:3352-3358).
+// KAD_RT_KERNEL=lane forces the general (wave per query) kernel, as it forces the lane kernel for rows; in the
+// KAD_ABLATIONS tools build KAD_RESP_KERNEL=noshortcut | stats selects the timing / statistics variants.
+static int resp_launch(const kad_table* t4, const kad_table* t6, bool dual, const uint8_t* self_id,
+                       const uint8_t* targets, uint32_t q, uint32_t count, uint32_t min_nodes, uint8_t* out,
+                       hipStream_t s) {
+    DevTable empty{};
+    const DevTable& d4 = t4 ? t4->d : empty;
+    const DevTable& d6 = t6 ? t6->d : empty;
+    auto be32 = [&](int k) {
+        return ((uint32_t)self_id[k] << 24) | ((uint32_t)self_id[k + 1] << 16) | ((uint32_t)self_id[k + 2] << 8) |
+               (uint32_t)self_id[k + 3];
+    };
+    const uint64_t shi = ((uint64_t)be32(0) << 32) | be32(4);
+    const uint32_t s2 = be32(8), s3 = be32(12), s4 = be32(16);
+    const uint32_t need_n = std::max(min_nodes, 1u);
+    const char* ev = std::getenv("KAD_RT_KERNEL");
+    const bool lines = count <= 8 && ((d4.flags | (dual ? d6.flags : 0u)) & (TF_WS | TF_SL)) &&
+                       !(ev && std::strcmp(ev, "lane") == 0);
+    if (lines) {
+        int mode = 0;
+#ifdef KAD_ABLATIONS
+        const char* rv = std::getenv("KAD_RESP_KERNEL");
+        if (rv && std::strcmp(rv, "noshortcut") == 0) mode = 1;
+        if (rv && std::strcmp(rv, "stats") == 0 && !dual) mode = 2;
+#endif
+        void (*k)(DevTable, DevTable, uint64_t, uint32_t, uint32_t, uint32_t, const uint8_t*, uint32_t, uint32_t,
+                  uint32_t, uint8_t*) = dual ? resp_line_kernel<0, true> : resp_line_kernel<0, false>;
+#ifdef KAD_ABLATIONS
+        if (mode == 1) k = dual ? resp_line_kernel<1, true> : resp_line_kernel<1, false>;
+        if (mode == 2) k = resp_line_kernel<2, false>;
+#endif
+        (void)mode;
+        hipLaunchKernelGGL(k, dim3(grid_for(q)), dim3(BLOCK), 0, s, d4, d6, shi, s2, s3, s4, targets, q, count, need_n,
+                           out);
+    } else {
+        if ((uint64_t)q > 0xFFFFFFFFull / 4 * BLOCK / 64) return set_err(KAD_ERR_INVALID, "batch too large");
+        hipLaunchKernelGGL(resp_wave_kernel, dim3((q + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, s, d4, d6,
+                           dual ? 1u : 0u, shi, s2, s3, s4, targets, q, count, need_n, out);
+    }
+    HIP_TRY(hipGetLastError());
+    return KAD_OK;
+}
+
+int kad_rt_responsible_batch(const kad_table* t, const uint8_t* self_id, const uint8_t* targets, uint32_t q,
+                             uint32_t count, uint32_t min_nodes, uint8_t* out_far, void* stream) {
+    if (!t) return set_err(KAD_ERR_INVALID, "NULL table");
+    if (!self_id || !targets || !out_far) return set_err(KAD_ERR_INVALID, "NULL buffer");
+    if (q == 0) return KAD_OK;
+    int rc = check_count(count);
+    if (rc) return rc;
+    if ((uintptr_t)targets & 3) return set_err(KAD_ERR_INVALID, "device buffers must be 4-byte aligned");
+    DeviceGuard g(t->device);
+    return resp_launch(t, nullptr, false, self_id, targets, q, count, min_nodes, out_far, (hipStream_t)stream);
+}
+
+int kad_rt_responsible_batch_dual(const kad_table* t4, const kad_table* t6, const uint8_t* self_id,
+                                  const uint8_t* targets, uint32_t q, uint32_t count, uint32_t min_nodes, uint8_t* out,
+                                  void* stream) {
+    if (!t4 && !t6) return set_err(KAD_ERR_INVALID, "both tables NULL");
+    if (!self_id || !targets || !out) return set_err(KAD_ERR_INVALID, "NULL buffer");
+    if (t4 && t6 && t4->device != t6->device) return set_err(KAD_ERR_INVALID, "tables on different devices");
+    if (q == 0) return KAD_OK;
+    int rc = check_count(count);
+    if (rc) return rc;
+    if ((uintptr_t)targets & 3) return set_err(KAD_ERR_INVALID, "device buffers must be 4-byte aligned");
+    DeviceGuard g(t4 ? t4->device : t6->device);
+    return resp_launch(t4, t6, true, self_id, targets, q, count, min_nodes, out, (hipStream_t)stream);
+}
+
+int kad_rt_responsible_batch_host(const kad_table* t, const uint8_t* self_id, const uint8_t* targets, uint32_t q,
+                                  uint32_t count, uint32_t min_nodes, uint8_t* out_far) {
+    if (!t) return set_err(KAD_ERR_INVALID, "NULL table");
+    if (!self_id || !targets || !out_far) return set_err(KAD_ERR_INVALID, "NULL buffer");
+    if (q == 0) return KAD_OK;
+    int rc = check_count(count);
+    if (rc) return rc;
+    DeviceGuard g(t->device);
+    // buffers and a stream of the call's own (nothing held by the table), ordered after the table's last
+    // asynchronous status refresh, whatever its stream (every other change to a table is synchronous)
+    uint8_t* dt = nullptr;
+    uint8_t* df = nullptr;
+    hipStream_t s = nullptr;
+    auto done = [&](int r) {
+        if (s) (void)hipStreamDestroy(s);
+        if (dt) (void)hipFree(dt);
+        if (df) (void)hipFree(df);
+        return r;
+    };
+    if (hipMalloc((void**)&dt, 20ull * q) != hipSuccess || hipMalloc((void**)&df, q) != hipSuccess) {
+        (void)hipGetLastError();
+        return done(set_err(KAD_ERR_NOMEM, "responsible host batch: out of device memory"));
+    }
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess)
+        return done(set_err(KAD_ERR_HIP, "responsible host batch: no stream"));
+    if (t->mut_async && hipStreamWaitEvent(s, t->mut_ev, 0) != hipSuccess)
+        return done(set_err(KAD_ERR_HIP, "responsible host batch: wait failed"));
+    if (hipMemcpyAsync(dt, targets, 20ull * q, hipMemcpyHostToDevice, s) != hipSuccess)
+        return done(set_err(KAD_ERR_HIP, "responsible host batch: H2D failed"));
+    rc = resp_launch(t, nullptr, false, self_id, dt, q, count, min_nodes, df, s);
+    if (rc == KAD_OK && hipMemcpyAsync(out_far, df, q, hipMemcpyDeviceToHost, s) != hipSuccess)
+        rc = set_err(KAD_ERR_HIP, "responsible host batch: D2H failed");
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rc == KAD_OK && e != hipSuccess) rc = set_err(KAD_ERR_HIP, "responsible host batch: %s", hipGetErrorString(e));
+    return done(rc);
 }
 
 static int shard_batch(const kad_table* t, const uint32_t* global_good_prefix, uint32_t global_buckets,

@@ -23,6 +23,14 @@ def _as_ids(a) -> np.ndarray:
     return a
 
 
+def _self_id(self_id) -> np.ndarray:
+    a = np.ascontiguousarray(np.frombuffer(bytes(self_id), np.uint8) if isinstance(self_id, (bytes, bytearray))
+                             else self_id, dtype=np.uint8).reshape(-1)
+    if a.shape != (20,):
+        raise ValueError(f"self_id must be 20 bytes, got {a.shape}")
+    return a
+
+
 def _stream_of(t, stream):
     if stream is not None:  # a raw hipStream_t handle or a torch.cuda.Stream
         return C.c_void_p(getattr(stream, "cuda_stream", stream))
@@ -277,7 +285,31 @@ class DeviceTable:
               "kad_rt_find_bucket_batch")
         return out
 
+    def rt_responsible(self, targets, self_id, count: int = 8, min_nodes: int = 1, out=None, stream=None):
+        """Storage-responsibility verdicts (kad_rt_responsible_batch; Dht::maintainStorage count 8 / min_nodes 1,
+        Dht::onAnnounce count 14 / min_nodes 8) over a (q, 20) uint8 device tensor of targets: one uint8 per
+        target, KAD_RESP_FAR where the last of its `count` closest good nodes is closer to it than self_id."""
+        import torch
+
+        q = targets.shape[0]
+        sid = _self_id(self_id)
+        if out is None:
+            out = torch.empty((q,), dtype=torch.uint8, device=targets.device)
+        check(lib().kad_rt_responsible_batch(self._h, ptr(sid), ptr(targets), q, count, min_nodes, ptr(out),
+                                             _stream_of(self, stream)), "kad_rt_responsible_batch")
+        return out
+
     # -- host-pointer synchronous queries ---------------------------------------------------
+    def rt_responsible_host(self, targets, self_id, count: int = 8, min_nodes: int = 1):
+        """rt_responsible over host targets, synchronous (kad_rt_responsible_batch_host). Returns (q,) uint8."""
+        t = _as_ids(targets)
+        q = t.shape[0]
+        sid = _self_id(self_id)
+        out = np.empty((q,), dtype=np.uint8)
+        check(lib().kad_rt_responsible_batch_host(self._h, ptr(sid), ptr(t), q, count, min_nodes, ptr(out)),
+              "kad_rt_responsible_batch_host")
+        return out
+
     def rt_closest_host(self, targets, count: int):
         t = _as_ids(targets)
         q = t.shape[0]
@@ -311,6 +343,24 @@ def rt_closest_dual(table4: DeviceTable | None, table6: DeviceTable | None, targ
                                           ptr(targets), ptr(af), q, count, ptr(out_idx), ptr(out_cnt), s),
           "kad_rt_closest_batch_dual")
     return out_idx, out_cnt
+
+
+def rt_responsible_dual(table4: DeviceTable | None, table6: DeviceTable | None, targets, self_id, count: int = 8,
+                        min_nodes: int = 1, stream=None):
+    """Dht::maintainStorage's verdict from both families in one launch (kad_rt_responsible_batch_dual): one uint8
+    per target, bit 0 (KAD_RESP_FAR4) far in table4, bit 1 (KAD_RESP_FAR6) far in table6; None = an empty table.
+    3 is maintainStorage's "discard"."""
+    import torch
+
+    q = targets.shape[0]
+    sid = _self_id(self_id)
+    out = torch.empty((q,), dtype=torch.uint8, device=targets.device)
+    s = C.c_void_p(getattr(stream, "cuda_stream", stream)) if stream is not None else C.c_void_p(
+        torch.cuda.current_stream(targets.device).cuda_stream)
+    check(lib().kad_rt_responsible_batch_dual(table4.handle if table4 else None, table6.handle if table6 else None,
+                                              ptr(sid), ptr(targets), q, count, min_nodes, ptr(out), s),
+          "kad_rt_responsible_batch_dual")
+    return out
 
 
 def nc_closest_dual(table4: DeviceTable | None, table6: DeviceTable | None, targets, af, count: int, stream=None):
