@@ -358,6 +358,46 @@ int kad_rt_responsible_batch_dual(const kad_table* table4, const kad_table* tabl
 int kad_rt_responsible_batch_host(const kad_table* t, const uint8_t* self_id, const uint8_t* targets, uint32_t q,
                                   uint32_t count, uint32_t min_nodes, uint8_t* out_far);
 
+/* ---- onNewNode triage (Dht::onNewNode(node, 0), dht.cpp:867-936) ---- */
+/* What onNewNode would do with candidate ID x, decided against the table's status snapshot (refresh it to `now`
+ * first, as before queries). With b = findBucket(x), evaluated in this order:
+ *   KAD_NN_NONE     the table has no bucket (dht.cpp:871)                                   node = KAD_NO_NODE
+ *   KAD_NN_KNOWN    a node of b has x's 160-bit ID (:874-880)                               node = the lowest such index
+ *   KAD_NN_REPLACE  b holds a KAD_STATUS_EXPIRED node (:897-901)                            node = the first expired node in
+ *                                                                                          bucket order (KAD_OP_REPLACE's a)
+ *   KAD_NN_INSERT   b holds fewer than KAD_TARGET_NODES nodes (:932-935)                    node = KAD_NO_NODE
+ *   KAD_NN_SPLIT    b is full and (mybucket || (bootstrap && depth(b) < 6)) &&              node = the first node of b without
+ *                   (!dubious || n_buckets == 1) (:921)                                     KAD_STATUS_GOOD (the ping
+ *   KAD_NN_FULL     b is full otherwise: "cache it away" (:929-931)                         candidate of :906-919), or
+ *                                                                                          KAD_NO_NODE
+ * mybucket: findBucket(self_id) == b; dubious: some node of b lacks KAD_STATUS_GOOD; depth(b) is
+ * RoutingTable::depth (routing_table.cpp:59-65); a bucket with more than KAD_TARGET_NODES nodes counts as full.
+ * Whether the ping candidate has a pending message is host state: the host checks it and walks on itself if so.
+ * verdict[i] = kind | KAD_NN_MYBUCKET when mybucket holds (every kind but NONE; the host needs it for
+ * mybucket_grow_time, :887-894). node[i] carries index_base, as the rows do. bucket[i] (may be NULL) = findBucket(x),
+ * KAD_NO_NODE for NONE: KAD_OP_SPLIT's operand, equal to kad_rt_find_bucket_batch on the same IDs.
+ * The candidates of one batch do not see each other: every verdict is against the snapshot.
+ * self_id: 20 host bytes or NULL (no bucket is "mine": a shard without the node's own ID); ids: device, q x 20
+ * bytes; verdict: device, q bytes; node, bucket: device, q words. flags: KAD_NN_BOOTSTRAP = Dht::is_bootstrap.
+ * Enqueues on `stream` and does not synchronise; a const query without table-held scratch: concurrent calls on
+ * distinct streams are safe. Checked in this order, before the table is read or any device work: NULL table, NULL
+ * ids / verdict / node, unknown flag bits (KAD_ERR_INVALID, also with q == 0); q == 0 (KAD_OK). */
+#define KAD_NN_NONE 0u
+#define KAD_NN_KNOWN 1u
+#define KAD_NN_REPLACE 2u
+#define KAD_NN_INSERT 3u
+#define KAD_NN_SPLIT 4u
+#define KAD_NN_FULL 5u
+#define KAD_NN_KIND_MASK 0x0Fu
+#define KAD_NN_MYBUCKET 0x10u
+#define KAD_NN_BOOTSTRAP 1u   /* flags: Dht::is_bootstrap */
+int kad_rt_triage_batch(const kad_table* t, const uint8_t* self_id, const uint8_t* ids, uint32_t q, uint32_t flags,
+                        uint8_t* verdict, uint32_t* node, uint32_t* bucket, void* stream);
+/* kad_rt_triage_batch on host buffers, synchronous, ordered after every change made to the table before the call;
+ * device buffers and a stream of the call's own. */
+int kad_rt_triage_batch_host(const kad_table* t, const uint8_t* self_id, const uint8_t* ids, uint32_t q,
+                             uint32_t flags, uint8_t* verdict, uint32_t* node, uint32_t* bucket);
+
 /* Per-query family select for NodeCache::getCachedNodes(id, sa_family, count) (node_cache.cpp:36-66:
  * cache_4 or cache_6 by family; Dht::refill asks the search's family, dht.cpp:1650): af[i] = 0 -> table4,
  * 1 -> table6 (KAD_TABLE_SORTED tables; either may be NULL = an empty map). Any count (as kad_nc_closest_batch).

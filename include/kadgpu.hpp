@@ -119,6 +119,17 @@ public:
                      "kad_rt_responsible_batch_host");
     }
 
+    /* onNewNode triage verdicts on host buffers (kad_rt_triage_batch_host); self_id may be NULL. */
+    void triageBatch(const uint8_t* self_id, const uint8_t* ids, size_t q, uint32_t flags, std::vector<uint8_t>& verdict,
+                     std::vector<uint32_t>& node, std::vector<uint32_t>& bucket) const {
+        verdict.resize(q);
+        node.resize(q);
+        bucket.resize(q);
+        if (q) check(kad_rt_triage_batch_host(t_, self_id, ids, (uint32_t)q, flags, verdict.data(), node.data(),
+                                              bucket.data()),
+                     "kad_rt_triage_batch_host");
+    }
+
     /* Node liveness (kad_table_set_times / kad_table_patch_times) and the device-side isGood(now)
      * refresh (kad_table_refresh_status, incremental). */
     void setTimes(const std::vector<int64_t>& time_ns, const std::vector<int64_t>& reply_ns,
@@ -142,6 +153,14 @@ public:
 
 private:
     kad_table* t_ = nullptr;
+};
+
+/* One candidate's onNewNode triage (kad_rt_triage_batch): verdict = KAD_NN_* kind | KAD_NN_MYBUCKET, node = the
+ * mirror's node index the kind names (KAD_NO_NODE if none), bucket = findBucket(id) (KAD_NO_NODE for KAD_NN_NONE). */
+struct NewNodeVerdict {
+    uint8_t verdict;
+    uint32_t node;
+    uint32_t bucket;
 };
 
 /* time_point -> int64 nanoseconds of its clock, time_point::min()/max() -> INT64_MIN/MAX (Node::time and
@@ -291,6 +310,30 @@ public:
                                        size_t count = KAD_TARGET_NODES, size_t min_nodes = 1) const {
         return isTooFarBatch(ids.data(), ids.size(), myid, now, count, min_nodes);
     }
+
+    /* What Dht::onNewNode(node, 0) (dht.cpp:867-936) would do with each candidate ID, taken alone against the table
+     * as mirrored and the statuses at `now`: KNOWN / REPLACE / INSERT / SPLIT / FULL (or NONE without a bucket), the
+     * node the kind names (the known node, the expired node to replace, the dubious node to ping; node(v.node)
+     * gives its pointer) and the bucket index. myid NULL: no bucket is "mine". The host-only parts stay with the
+     * caller: trySearchInsert for every kind but KNOWN, mybucket_grow_time when KAD_NN_MYBUCKET is set, b->cached
+     * for FULL, and isPendingMessage() of the ping candidate (walk on from it in the bucket when it has one). One
+     * kad_rt_triage_batch_host call, after the same refresh isTooFarBatch takes. */
+    template <class InfoHashT, class TimePoint>
+    std::vector<NewNodeVerdict> onNewNodeBatch(const InfoHashT* ids, size_t q, const InfoHashT* myid, TimePoint now,
+                                               bool is_bootstrap) const {
+        std::vector<NewNodeVerdict> out(q);
+        if (q == 0) return out;
+        advance(to_ns(now));
+        std::vector<uint8_t> cand(q * KAD_HASH_LEN), verdict;
+        std::vector<uint32_t> node, bucket;
+        for (size_t i = 0; i < q; i++) std::memcpy(&cand[i * KAD_HASH_LEN], id_bytes(ids[i]), KAD_HASH_LEN);
+        table_.triageBatch(myid ? id_bytes(*myid) : nullptr, cand.data(), q, is_bootstrap ? KAD_NN_BOOTSTRAP : 0u, verdict,
+                           node, bucket);
+        for (size_t i = 0; i < q; i++) out[i] = NewNodeVerdict{verdict[i], node[i], bucket[i]};
+        return out;
+    }
+    /* The mirrored node of a NewNodeVerdict's index. */
+    const NodePtr& node(uint32_t index) const { return nodes_[index]; }
 
     /* A mirrored node's time / reply_time / expired_ changed (Node::received, setExpired, reset,
      * Search::insertNode writing node->time): re-read at the next query. */
@@ -715,6 +758,13 @@ public:
         for (size_t i = 0; i < out.size(); i++)
             out[i] = (uint8_t)((a[i] ? KAD_RESP_FAR4 : 0u) | (b[i] ? KAD_RESP_FAR6 : 0u));
         return out;
+    }
+    /* Dht::onNewNode(node, 0) triage for the candidates of one family (RoutingTableMirror::onNewNodeBatch), at the
+     * mirror's clock. */
+    template <class InfoHashT>
+    std::vector<NewNodeVerdict> onNewNodeBatch(const InfoHashT* ids, size_t q, sa_family_t af, const InfoHashT* myid,
+                                               bool is_bootstrap) const {
+        return buckets(af).onNewNodeBatch(ids, q, myid, clock_(), is_bootstrap);
     }
     /* Dht::buckets(af) (dht.h:437-438) */
     const RoutingTableMirror<RoutingTableT>& buckets(sa_family_t af) const { return af == AF_INET ? v4_ : v6_; }

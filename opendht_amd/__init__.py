@@ -9,10 +9,15 @@ from ._lib import (KAD_MAX_COUNT, KAD_NO_NODE, KAD_SEARCH_NODES, KAD_STATUS_EXPI
                    KAD_TARGET_NODES, KadError, lib)
 from .infohash import InfoHash, zeroes
 from ._lib import KAD_RESP_FAR, KAD_RESP_FAR4, KAD_RESP_FAR6
+from ._lib import (KAD_NN_BOOTSTRAP, KAD_NN_FULL, KAD_NN_INSERT, KAD_NN_KIND_MASK, KAD_NN_KNOWN, KAD_NN_MYBUCKET,
+                   KAD_NN_NONE, KAD_NN_REPLACE, KAD_NN_SPLIT)
+from .ingest import ingest
 from .table import DeviceTable, nc_closest_dual, rt_closest_dual, rt_responsible_dual
 
 __all__ = [
     "DeviceTable", "InfoHash", "KadError", "KAD_MAX_COUNT", "KAD_NO_NODE", "KAD_SEARCH_NODES",
     "KAD_STATUS_EXPIRED", "KAD_STATUS_GOOD", "KAD_TARGET_NODES", "lib", "nc_closest_dual", "rt_closest_dual", "zeroes",
     "KAD_RESP_FAR", "KAD_RESP_FAR4", "KAD_RESP_FAR6", "rt_responsible_dual",
+    "KAD_NN_BOOTSTRAP", "KAD_NN_FULL", "KAD_NN_INSERT", "KAD_NN_KIND_MASK", "KAD_NN_KNOWN", "KAD_NN_MYBUCKET",
+    "KAD_NN_NONE", "KAD_NN_REPLACE", "KAD_NN_SPLIT", "ingest",
 ]

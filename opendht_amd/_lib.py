@@ -36,6 +36,8 @@ KAD_INFO_SLOT_LINES = 0x2000
 KAD_SERVE_MAX_Q, KAD_SERVE_MAX_COUNT, KAD_SERVE_MAX_IDLE_US = 64, 64, 1000000
 KAD_OP_REMOVE, KAD_OP_REPLACE, KAD_OP_INSERT, KAD_OP_SPLIT = 1, 2, 3, 4
 KAD_RESP_FAR, KAD_RESP_FAR4, KAD_RESP_FAR6 = 1, 1, 2
+KAD_NN_NONE, KAD_NN_KNOWN, KAD_NN_REPLACE, KAD_NN_INSERT, KAD_NN_SPLIT, KAD_NN_FULL = 0, 1, 2, 3, 4, 5
+KAD_NN_KIND_MASK, KAD_NN_MYBUCKET, KAD_NN_BOOTSTRAP = 0x0F, 0x10, 1
 
 
 def row_words(count: int) -> int:
@@ -130,6 +132,8 @@ SIGNATURES = {
     "kad_rt_responsible_batch": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
     "kad_rt_responsible_batch_dual": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
     "kad_rt_responsible_batch_host": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P]),
+    "kad_rt_triage_batch": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
+    "kad_rt_triage_batch_host": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "kad_rt_shard_batch": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
                                      _P, _P]),

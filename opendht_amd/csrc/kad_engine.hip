@@ -2725,6 +2725,181 @@ __global__ __launch_bounds__(BLOCK) void resp_wave_kernel(DevTable T4, DevTable 
     if ((threadIdx.x & 63u) == 0) out[i] = (uint8_t)far;
 }
 
+// ---------------------------------------------------------------------------------------
+// onNewNode triage verdicts (kad_rt_triage_batch): Dht::onNewNode(node, 0) (dht.cpp:867-936) decided against the
+// table's status snapshot, one byte and one node index per candidate instead of a host walk of its bucket. With
+// b = findBucket(x), in this order: no bucket NONE; a node of b with x's 160-bit ID KNOWN (the lowest such index);
+// an expired node in b REPLACE (the first in bucket order); fewer than KAD_TARGET_NODES nodes INSERT; else the bucket
+// is full: SPLIT when (mybucket || (bootstrap && depth(b) < 6)) && (!dubious || B == 1) (dht.cpp:921), FULL
+// otherwise, both with the first non-good node of b (the ping candidate of dht.cpp:906-919) or NONE.
+//
+// Buckets of at most 32 nodes: the lane reads dir[b] and dir[b+1].x, then the bucket's keys and status bytes eight
+// at a time, all in flight together; a node's tail is read only when its key equals the candidate's top 64 bits.
+// Every step is a random 64-byte line or two and the steps depend on each other (candidate, directory, keys and
+// status, tail). Loading the status bytes only once no node has the candidate's ID saves known candidates a line
+// but gives new ones a fourth dependent step: measured slower on every mix, kept as the
+// tools-build form KAD_TRIAGE_KERNEL=deferred.
+// "dubious" and the first non-good node come from the directory's good mask dir[b].y, which every writer of status[] keeps current (kad_table_create, bucket_good_kernel after an apply or a
+// full update, bucket_good_dirty_kernel and the fused refresh after patch_status / refresh_status). WIDE buckets
+// (no mask) are taken by the whole wave, one candidate after the other, with ballots over 64-node chunks.
+// depth(b) (routing_table.cpp:59-65) is restated from the bucket firsts and read only by full buckets that are not
+// "mine" under bootstrap.
+// ---------------------------------------------------------------------------------------
+
+// InfoHash::lowbit (infohash.h): the index, counted from the most significant bit, of the lowest set bit; -1 for zero.
+__device__ __forceinline__ int lowbit160(uint64_t hi, uint32_t a, uint32_t b, uint32_t c) {
+    if (c) return 159 - (int)__builtin_ctz(c);
+    if (b) return 127 - (int)__builtin_ctz(b);
+    if (a) return 95 - (int)__builtin_ctz(a);
+    if (hi) return 63 - (int)__builtin_ctzll(hi);
+    return -1;
+}
+
+// RoutingTable::depth (routing_table.cpp:59-65)
+__device__ __forceinline__ uint32_t bucket_depth(const DevTable& T, uint32_t b) {
+    const uint32_t* f = T.ftail + 3ull * b;
+    int d = lowbit160(T.fkey[b], f[0], f[1], f[2]);
+    if (b + 1 < T.B) d = max(d, lowbit160(T.fkey[b + 1], f[3], f[4], f[5]));
+    return (uint32_t)(d + 1);
+}
+
+// The verdict of a bucket whose walk found no equal ID: n nodes, the first expired node (bucket-relative, NONE if
+// none), the first non-good node (likewise). mine: findBucket(self_id) == b.
+__device__ __forceinline__ uint32_t triage_decide(const DevTable& T, uint32_t b, uint32_t j0, uint32_t n, uint32_t fexp,
+                                                  uint32_t fbad, bool mine, uint32_t bootstrap, uint32_t& nd) {
+    if (fexp != NONE) {
+        nd = j0 + fexp + T.index_base;
+        return KAD_NN_REPLACE;
+    }
+    if (n < KAD_TARGET_NODES) {
+        nd = NONE;
+        return KAD_NN_INSERT;
+    }
+    nd = fbad != NONE ? j0 + fbad + T.index_base : NONE;
+    const bool ok = fbad == NONE || T.B == 1;
+    if (ok && (mine || (bootstrap && bucket_depth(T, b) < 6u))) return KAD_NN_SPLIT;
+    return KAD_NN_FULL;
+}
+
+// One lane per candidate; the candidates of WIDE buckets one after the other by the wave. sb = findBucket(self_id)
+// is kernel-uniform (has_self == 0: no bucket is "mine"). EAGER: the status bytes are loaded with the keys, for every candidate
+// (the product form); !EAGER (KAD_ABLATIONS tools build, KAD_TRIAGE_KERNEL=deferred): after the key compare.
+template <bool EAGER>
+__global__ __launch_bounds__(BLOCK) void triage_kernel(DevTable T, uint64_t shi, uint32_t s2, uint32_t s3, uint32_t s4,
+                                                       uint32_t has_self, uint32_t bootstrap,
+                                                       const uint8_t* __restrict__ ids, uint32_t q,
+                                                       uint8_t* __restrict__ verdict, uint32_t* __restrict__ node,
+                                                       uint32_t* __restrict__ bucket) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x, lane = threadIdx.x & 63u;
+    const bool act = i < q;
+    if (T.B == 0) {  // kernel-uniform: list.end() (dht.cpp:871)
+        if (act) {
+            __builtin_nontemporal_store((uint8_t)KAD_NN_NONE, verdict + i);
+            st_row1(node + i, NONE);
+            if (bucket) st_row1(bucket + i, NONE);
+        }
+        return;
+    }
+    const uint32_t sb = has_self ? locate_bucket(T, Target{shi, s2, s3, s4}) : NONE;
+    Target t{};
+    uint32_t b = 0, j0 = 0, n = 0, kind = KAD_NN_NONE, nd = NONE;
+    bool wide = false;
+    if (act) {
+        t = load_target(ids, i);
+        b = locate_bucket(T, t);
+        const uint2 d0 = T.dir[b];
+        j0 = d0.x & ~WIDE;
+        n = (T.dir[b + 1].x & ~WIDE) - j0;
+        wide = (d0.x & WIDE) != 0;
+        if (!wide) {  // n <= 32
+            // Eight loads in flight per chunk, none predicated; an index past the bucket's end is clamped to its last
+            // node, so no load touches a line the bucket does not own.
+            uint32_t eqm = 0, exm = 0;
+            for (uint32_t c = 0; c < n; c += 8) {
+                uint64_t k[8];
+                uint32_t st[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) k[u] = T.key[j0 + min(c + u, n - 1u)];
+                if (EAGER) {
+#pragma unroll
+                    for (int u = 0; u < 8; u++) st[u] = T.status[j0 + min(c + u, n - 1u)];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const bool in = c + u < n;
+                    eqm |= (in && k[u] == t.hi ? 1u : 0u) << (c + u);
+                    if (EAGER) exm |= (in && (st[u] & KAD_STATUS_EXPIRED) ? 1u : 0u) << (c + u);
+                }
+            }
+            uint32_t known = NONE;
+            for (; eqm; eqm &= eqm - 1) {  // a key match is rare: only now the tail
+                const uint32_t j = j0 + (uint32_t)__builtin_ctz(eqm);
+                const uint32_t* tl = T.tail + 3ull * j;
+                if (tl[0] == t.t2 && tl[1] == t.t3 && tl[2] == t.t4) {
+                    known = j;
+                    break;
+                }
+            }
+            if (known != NONE) {
+                kind = KAD_NN_KNOWN;
+                nd = known + T.index_base;
+            } else {
+                if (!EAGER) {  // status bytes (expired): only now, a known candidate never needs them
+                    for (uint32_t c = 0; c < n; c += 8) {
+                        uint32_t st[8];
+#pragma unroll
+                        for (int u = 0; u < 8; u++) st[u] = T.status[j0 + min(c + u, n - 1u)];
+#pragma unroll
+                        for (int u = 0; u < 8; u++)
+                            exm |= (c + u < n && (st[u] & KAD_STATUS_EXPIRED) ? 1u : 0u) << (c + u);
+                    }
+                }
+                const uint32_t all = n >= 32 ? ~0u : (1u << n) - 1u, bad = ~d0.y & all;
+                kind = triage_decide(T, b, j0, n, exm ? (uint32_t)__builtin_ctz(exm) : NONE,
+                                     bad ? (uint32_t)__builtin_ctz(bad) : NONE, b == sb, bootstrap, nd);
+            }
+        }
+    }
+    for (uint64_t mk = __ballot(act && wide); mk; mk &= mk - 1) {  // WIDE buckets: the wave, 64 nodes at a time
+        const uint32_t l = (uint32_t)__builtin_ctzll(mk);
+        const uint64_t uhi = rdl64(t.hi, l);
+        const uint32_t u2 = rdl(t.t2, l), u3 = rdl(t.t3, l), u4 = rdl(t.t4, l);
+        const uint32_t ub = rdl(b, l), uj0 = rdl(j0, l), un = rdl(n, l);
+        uint32_t known = NONE, fexp = NONE, fbad = NONE;
+        for (uint32_t c = 0; c < un && known == NONE; c += 64) {
+            const uint32_t r = c + lane;
+            const bool in = r < un;
+            bool eq = in && T.key[uj0 + r] == uhi;
+            const uint32_t st = in ? T.status[uj0 + r] : (uint32_t)KAD_STATUS_GOOD;
+            if (eq) {
+                const uint32_t* tl = T.tail + 3ull * (uj0 + r);
+                eq = tl[0] == u2 && tl[1] == u3 && tl[2] == u4;
+            }
+            const uint64_t eqb = __ballot(eq), exb = __ballot((st & KAD_STATUS_EXPIRED) != 0),
+                           bdb = __ballot(!(st & KAD_STATUS_GOOD));
+            if (eqb) known = c + (uint32_t)__builtin_ctzll(eqb);
+            if (fexp == NONE && exb) fexp = c + (uint32_t)__builtin_ctzll(exb);
+            if (fbad == NONE && bdb) fbad = c + (uint32_t)__builtin_ctzll(bdb);
+        }
+        uint32_t wk, wn;
+        if (known != NONE) {
+            wk = KAD_NN_KNOWN;
+            wn = uj0 + known + T.index_base;
+        } else {
+            wk = triage_decide(T, ub, uj0, un, fexp, fbad, ub == sb, bootstrap, wn);
+        }
+        if (lane == l) {
+            kind = wk;
+            nd = wn;
+        }
+    }
+    if (act) {
+        __builtin_nontemporal_store((uint8_t)(kind | (b == sb ? KAD_NN_MYBUCKET : 0u)), verdict + i);
+        st_row1(node + i, nd);
+        if (bucket) st_row1(bucket + i, b);
+    }
+}
+
 // Fallback slot lines (dw1 == NONE) and those without a bucket (dw0 == NONE): cnt[0], cnt[1] (KAD_DEBUG).
 __global__ void sl_count_kernel(const uint32_t* sl, uint32_t slslots, uint32_t* cnt) {
     const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
@@ -9746,6 +9921,85 @@ int kad_rt_responsible_batch_host(const kad_table* t, const uint8_t* self_id, co
         rc = set_err(KAD_ERR_HIP, "responsible host batch: D2H failed");
     const hipError_t e = hipStreamSynchronize(s);
     if (rc == KAD_OK && e != hipSuccess) rc = set_err(KAD_ERR_HIP, "responsible host batch: %s", hipGetErrorString(e));
+    return done(rc);
+}
+
+// onNewNode triage verdicts (Dht::onNewNode dht.cpp:867-936): one launch, no scratch. In the KAD_ABLATIONS tools build
+// KAD_TRIAGE_KERNEL=deferred selects the form that loads the status bytes after the key compare (same results, for
+// timing).
+static int triage_launch(const kad_table* t, const uint8_t* self_id, const uint8_t* ids, uint32_t q, uint32_t flags,
+                         uint8_t* verdict, uint32_t* node, uint32_t* bucket, hipStream_t s) {
+    auto be32 = [&](int k) {
+        return ((uint32_t)self_id[k] << 24) | ((uint32_t)self_id[k + 1] << 16) | ((uint32_t)self_id[k + 2] << 8) |
+               (uint32_t)self_id[k + 3];
+    };
+    uint64_t shi = 0;
+    uint32_t s2 = 0, s3 = 0, s4 = 0;
+    if (self_id) {
+        shi = ((uint64_t)be32(0) << 32) | be32(4);
+        s2 = be32(8);
+        s3 = be32(12);
+        s4 = be32(16);
+    }
+    void (*k)(DevTable, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t*, uint32_t, uint8_t*,
+              uint32_t*, uint32_t*) = triage_kernel<true>;
+#ifdef KAD_ABLATIONS
+    const char* ev = std::getenv("KAD_TRIAGE_KERNEL");
+    if (ev && std::strcmp(ev, "deferred") == 0) k = triage_kernel<false>;
+#endif
+    hipLaunchKernelGGL(k, dim3(grid_for(q)), dim3(BLOCK), 0, s, t->d, shi, s2, s3, s4, self_id ? 1u : 0u,
+                       (flags & KAD_NN_BOOTSTRAP) ? 1u : 0u, ids, q, verdict, node, bucket);
+    HIP_TRY(hipGetLastError());
+    return KAD_OK;
+}
+
+int kad_rt_triage_batch(const kad_table* t, const uint8_t* self_id, const uint8_t* ids, uint32_t q, uint32_t flags,
+                        uint8_t* verdict, uint32_t* node, uint32_t* bucket, void* stream) {
+    if (!t) return set_err(KAD_ERR_INVALID, "NULL table");
+    if (!ids || !verdict || !node) return set_err(KAD_ERR_INVALID, "NULL buffer");
+    if (flags & ~KAD_NN_BOOTSTRAP) return set_err(KAD_ERR_INVALID, "unknown triage flags 0x%x", flags);
+    if (q == 0) return KAD_OK;
+    if (((uintptr_t)ids | (uintptr_t)node | (uintptr_t)bucket) & 3)
+        return set_err(KAD_ERR_INVALID, "device buffers must be 4-byte aligned");
+    DeviceGuard g(t->device);
+    return triage_launch(t, self_id, ids, q, flags, verdict, node, bucket, (hipStream_t)stream);
+}
+
+int kad_rt_triage_batch_host(const kad_table* t, const uint8_t* self_id, const uint8_t* ids, uint32_t q, uint32_t flags,
+                             uint8_t* verdict, uint32_t* node, uint32_t* bucket) {
+    if (!t) return set_err(KAD_ERR_INVALID, "NULL table");
+    if (!ids || !verdict || !node) return set_err(KAD_ERR_INVALID, "NULL buffer");
+    if (flags & ~KAD_NN_BOOTSTRAP) return set_err(KAD_ERR_INVALID, "unknown triage flags 0x%x", flags);
+    if (q == 0) return KAD_OK;
+    DeviceGuard g(t->device);
+    // buffers and a stream of the call's own, ordered after the table's last asynchronous status refresh (as
+    // kad_rt_responsible_batch_host). One allocation: ids, then node, then bucket words, then the verdict bytes.
+    uint8_t* buf = nullptr;
+    hipStream_t s = nullptr;
+    auto done = [&](int r) {
+        if (s) (void)hipStreamDestroy(s);
+        if (buf) (void)hipFree(buf);
+        return r;
+    };
+    const size_t o_node = 20ull * q, o_bucket = o_node + 4ull * q, o_verdict = o_bucket + 4ull * q;
+    if (hipMalloc((void**)&buf, o_verdict + q) != hipSuccess) {
+        (void)hipGetLastError();
+        return done(set_err(KAD_ERR_NOMEM, "triage host batch: out of device memory"));
+    }
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess)
+        return done(set_err(KAD_ERR_HIP, "triage host batch: no stream"));
+    if (t->mut_async && hipStreamWaitEvent(s, t->mut_ev, 0) != hipSuccess)
+        return done(set_err(KAD_ERR_HIP, "triage host batch: wait failed"));
+    if (hipMemcpyAsync(buf, ids, 20ull * q, hipMemcpyHostToDevice, s) != hipSuccess)
+        return done(set_err(KAD_ERR_HIP, "triage host batch: H2D failed"));
+    int rc = triage_launch(t, self_id, buf, q, flags, buf + o_verdict, (uint32_t*)(buf + o_node),
+                           bucket ? (uint32_t*)(buf + o_bucket) : nullptr, s);
+    if (rc == KAD_OK && (hipMemcpyAsync(verdict, buf + o_verdict, q, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                         hipMemcpyAsync(node, buf + o_node, 4ull * q, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                         (bucket && hipMemcpyAsync(bucket, buf + o_bucket, 4ull * q, hipMemcpyDeviceToHost, s) != hipSuccess)))
+        rc = set_err(KAD_ERR_HIP, "triage host batch: D2H failed");
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rc == KAD_OK && e != hipSuccess) rc = set_err(KAD_ERR_HIP, "triage host batch: %s", hipGetErrorString(e));
     return done(rc);
 }
 

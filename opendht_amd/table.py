@@ -78,6 +78,7 @@ class DeviceTable:
         self.device = device
         self.n = n
         self.B = B
+        self.index_base = index_base
 
     # -- lifetime ------------------------------------------------------------------------
     def close(self) -> None:
@@ -299,7 +300,41 @@ class DeviceTable:
                                              _stream_of(self, stream)), "kad_rt_responsible_batch")
         return out
 
+    def rt_triage(self, ids, self_id=None, bootstrap: bool = False, want_bucket: bool = False, out=None, stream=None):
+        """Dht::onNewNode(node, 0) triage verdicts (kad_rt_triage_batch) over a (q, 20) uint8 device tensor of
+        candidate IDs, against the current status snapshot: (verdict (q,) uint8 = KAD_NN_* kind | KAD_NN_MYBUCKET,
+        node (q,) int32, bucket (q,) int32 or None). self_id None: no bucket is "mine". out: the same tuple of
+        tensors to write into."""
+        import torch
+
+        q = ids.shape[0]
+        sid = None if self_id is None else _self_id(self_id)
+        verdict, node, bucket = out if out is not None else (None, None, None)
+        if verdict is None:
+            verdict = torch.empty((q,), dtype=torch.uint8, device=ids.device)
+        if node is None:
+            node = torch.empty((q,), dtype=torch.int32, device=ids.device)
+        if bucket is None and want_bucket:
+            bucket = torch.empty((q,), dtype=torch.int32, device=ids.device)
+        check(lib().kad_rt_triage_batch(self._h, ptr(sid), ptr(ids), q, _lib.KAD_NN_BOOTSTRAP if bootstrap else 0,
+                                        ptr(verdict), ptr(node), ptr(bucket), _stream_of(self, stream)),
+              "kad_rt_triage_batch")
+        return verdict, node, bucket
+
     # -- host-pointer synchronous queries ---------------------------------------------------
+    def rt_triage_host(self, ids, self_id=None, bootstrap: bool = False, want_bucket: bool = False):
+        """rt_triage over host IDs, synchronous (kad_rt_triage_batch_host): (verdict uint8, node uint32, bucket
+        uint32 or None) host arrays."""
+        t = _as_ids(ids)
+        q = t.shape[0]
+        sid = None if self_id is None else _self_id(self_id)
+        verdict = np.empty((q,), dtype=np.uint8)
+        node = np.empty((q,), dtype=np.uint32)
+        bucket = np.empty((q,), dtype=np.uint32) if want_bucket else None
+        check(lib().kad_rt_triage_batch_host(self._h, ptr(sid), ptr(t), q, _lib.KAD_NN_BOOTSTRAP if bootstrap else 0,
+                                             ptr(verdict), ptr(node), ptr(bucket)), "kad_rt_triage_batch_host")
+        return verdict, node, bucket
+
     def rt_responsible_host(self, targets, self_id, count: int = 8, min_nodes: int = 1):
         """rt_responsible over host targets, synchronous (kad_rt_responsible_batch_host). Returns (q,) uint8."""
         t = _as_ids(targets)
