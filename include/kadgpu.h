@@ -398,6 +398,71 @@ int kad_rt_triage_batch(const kad_table* t, const uint8_t* self_id, const uint8_
 int kad_rt_triage_batch_host(const kad_table* t, const uint8_t* self_id, const uint8_t* ids, uint32_t q,
                              uint32_t flags, uint8_t* verdict, uint32_t* node, uint32_t* bucket);
 
+/* ---- trySearchInsert verdicts over a set of live searches (Dht::trySearchInsert dht.cpp:816-849) ---- */
+/* A search set is one family's live searches: S searches in strictly ascending 160-bit ID order (the order of the
+ * std::map), each with a flag byte (KAD_SR_EXPIRED = Search::expired) and a node list of n entries (20-byte node ID,
+ * flag byte; KAD_SN_BAD = SearchNode::isBad(), dht.cpp:458-460) strictly ascending in XOR distance to the search's ID,
+ * the order Search::insertNode keeps. Node identity is the 160-bit ID (NodeCache holds one Node per ID and family).
+ *
+ * accept(s, x): s.insertNode(x, now) with an empty token would return true (dht.cpp:961-1047), from the snapshot alone:
+ *   1. x equals a node ID of the list: refuse, KAD_SR_STOP_KNOWN (:972-984).
+ *   2. the trim position t and `full` (:989-1007, kad_search_trim): expired: full = n >= 14, t = full ? 14 : n;
+ *      else bad = number of BAD entries, full = n - bad >= 14, t = n, and while t - bad > 14: --t, and --bad if
+ *      entry[t] is BAD.
+ *   3. full and x not strictly closer to s.id than entry[t-1]: refuse (:1009-1014), KAD_SR_STOP_FAR for a live
+ *      search, KAD_SR_STOP_FAR_EXPIRED for an expired one.
+ *   4. otherwise accept.
+ * Per candidate, with lb = lower_bound(search IDs, x) (the first search whose ID is >= x; S if none): fwd = the number
+ * of consecutive accepting searches lb, lb+1, ...; back = the number of consecutive accepting searches lb-1, lb-2,
+ * ...; stop = fstop | bstop << 4, why each walk ended (KAD_SR_STOP_END: it ran off the set). S == 0 gives lb = fwd =
+ * back = 0, stop = 0. The candidates of one batch do not see each other. node.time = now, removeExpiredNode, tokens
+ * and the scheduler edit stay on the host: what it does to the searches [lb - back, lb + fwd). */
+#define KAD_SR_EXPIRED 0x01u          /* search flag: Search::expired */
+#define KAD_SN_BAD 0x01u              /* node flag: SearchNode::isBad() */
+#define KAD_SR_STOP_END 0u
+#define KAD_SR_STOP_KNOWN 1u
+#define KAD_SR_STOP_FAR 2u
+#define KAD_SR_STOP_FAR_EXPIRED 3u
+typedef struct kad_searches kad_searches;
+/* Step 2 above on a list's flag bytes (host code, no device): *full = 0 or 1, *t <= n. NULL node_flags with n > 0,
+ * NULL full / t: KAD_ERR_INVALID (kad_last_error is not set: the function lives outside the engine). */
+int kad_search_trim(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t* full, uint32_t* t);
+/* Host arrays: ids S x 20 bytes, flags S bytes, the lists in CSR form (off[S + 1] into node_ids, 20 bytes each, and
+ * node_flags). The device keeps a fixed slab of `cap` entries per search and, per search, t, full and the threshold
+ * ID entry[t-1], derived on the host. Checked in this order, before any device work: NULL out / off, NULL ids / flags
+ * with S > 0, NULL node_ids / node_flags with off[S] > 0 (KAD_ERR_INVALID); cap < KAD_SEARCH_NODES
+ * (KAD_ERR_INVALID); search IDs not strictly ascending (KAD_ERR_INVALID); offsets not ascending or a list not strictly
+ * ascending in distance to its search ID, which also rejects duplicate nodes (KAD_ERR_INVALID); a list longer than cap
+ * (KAD_ERR_UNSUPPORTED: create again with a larger cap). S == 0 is a valid set. Synchronous. */
+int kad_searches_create(kad_searches** out, int device, uint32_t S, uint32_t cap, const uint8_t* ids,
+                        const uint8_t* flags, const uint32_t* off, const uint8_t* node_ids, const uint8_t* node_flags);
+/* Replaces the flags and lists of the m searches which[0..m) (strictly ascending, < S: KAD_ERR_INVALID otherwise):
+ * the ones the host's inserts changed. flags m bytes, off[m + 1], node arrays as for create, the same checks in the
+ * same order. The set of search IDs is fixed: adding or erasing a search is a new set. Synchronous, and as
+ * kad_table_apply towards queries: it first waits for all device work enqueued before the call, so a query enqueued
+ * earlier reads the old set and one enqueued after the return the new one; the caller must not enqueue queries on
+ * the set from another thread while the call runs. Failure leaves the set unchanged. m == 0: KAD_OK. */
+int kad_searches_patch(kad_searches* ss, uint32_t m, const uint32_t* which, const uint8_t* flags, const uint32_t* off,
+                       const uint8_t* node_ids, const uint8_t* node_flags);
+/* S, cap and the device bytes held (any may be NULL). */
+int kad_searches_info(const kad_searches* ss, uint32_t* S, uint32_t* cap, uint64_t* device_bytes);
+/* The device state read back into host arrays (any may be NULL): ids S x 20, flags S, n S words, node_ids
+ * S x cap x 20 and node_flags S x cap (the slabs; entries past n are zero), and the derived full (S bytes) and t
+ * (S words). */
+int kad_searches_export(const kad_searches* ss, uint8_t* ids, uint8_t* flags, uint32_t* n, uint8_t* node_ids,
+                        uint8_t* node_flags, uint8_t* full, uint32_t* t);
+int kad_searches_destroy(kad_searches* ss);
+/* The verdicts of q candidates. Device pointers: ids q x 20 bytes; out_lb (may be NULL), out_fwd, out_back q words;
+ * out_stop q bytes. Enqueues on `stream` and does not synchronise; a const query without set-held scratch: concurrent
+ * calls on distinct streams are safe. One lane per candidate; a walk over a run of accepting searches is serial in
+ * its lane. Checked in this order: NULL set, NULL ids / out_fwd / out_back / out_stop (KAD_ERR_INVALID, also with
+ * q == 0); q == 0 (KAD_OK); ids or a word output not 4-byte aligned (KAD_ERR_INVALID). */
+int kad_sr_try_insert_batch(const kad_searches* ss, const uint8_t* ids, uint32_t q, uint32_t* out_lb,
+                            uint32_t* out_fwd, uint32_t* out_back, uint8_t* out_stop, void* stream);
+/* kad_sr_try_insert_batch on host buffers, synchronous; device buffers and a stream of the call's own. */
+int kad_sr_try_insert_batch_host(const kad_searches* ss, const uint8_t* ids, uint32_t q, uint32_t* out_lb,
+                                 uint32_t* out_fwd, uint32_t* out_back, uint8_t* out_stop);
+
 /* Per-query family select for NodeCache::getCachedNodes(id, sa_family, count) (node_cache.cpp:36-66:
  * cache_4 or cache_6 by family; Dht::refill asks the search's family, dht.cpp:1650): af[i] = 0 -> table4,
  * 1 -> table6 (KAD_TABLE_SORTED tables; either may be NULL = an empty map). Any count (as kad_nc_closest_batch).

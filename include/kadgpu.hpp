@@ -724,11 +724,153 @@ private:
     NodeCacheFamilyMirror<NodeMapT> v4_, v6_;
 };
 
+/* One candidate's trySearchInsert verdict (kad_sr_try_insert_batch): the searches [lb - back, lb + fwd) in map
+ * order would take it; stop = fstop | bstop << 4 (KAD_SR_STOP_*), why each walk ended. */
+struct SearchInsertVerdict {
+    uint32_t lb, fwd, back;
+    uint8_t stop;
+};
+
+/* Device mirror of one family's live searches (Dht::searches(af), dht.h) over a map shaped like
+ * std::map<InfoHash, std::shared_ptr<Search>>. Reads of a search: id, expired, nodes[i].node->id, nodes[i].isBad().
+ * The map must outlive the mirror or the next snapshot. */
+template <class SearchMapT>
+class SearchesMirror {
+public:
+    SearchesMirror() {}
+    ~SearchesMirror() { reset(); }
+    SearchesMirror(const SearchesMirror&) = delete;
+    SearchesMirror& operator=(const SearchesMirror&) = delete;
+    SearchesMirror(SearchesMirror&& o) noexcept { swap(o); }
+    SearchesMirror& operator=(SearchesMirror&& o) noexcept {
+        if (this != &o) {
+            reset();
+            swap(o);
+        }
+        return *this;
+    }
+
+    /* Snapshot every search of `map`. cap: slab entries per search, grown to the longest list. */
+    void snapshot(const SearchMapT& map, int device = 0, uint32_t cap = 32) {
+        std::vector<uint8_t> ids, flags, nid, nfl;
+        std::vector<uint32_t> off(1, 0u);
+        for (const auto& kv : map) {
+            ids.insert(ids.end(), id_bytes(kv.first), id_bytes(kv.first) + KAD_HASH_LEN);
+            append(*kv.second, flags, off, nid, nfl);
+            cap = std::max<uint32_t>(cap, off.back() - off[off.size() - 2]);
+        }
+        kad_searches* ss = nullptr;
+        check(kad_searches_create(&ss, device, (uint32_t)flags.size(), cap, ids.data(), flags.data(), off.data(),
+                                  nid.data(), nfl.data()), "kad_searches_create");
+        reset();
+        ss_ = ss;
+        map_ = &map;
+        ids_.swap(ids);
+        device_ = device;
+        cap_ = cap;
+    }
+
+    /* The searches with these IDs changed their list or flags (the host's inserts, a node turning bad, expiry):
+     * one kad_searches_patch. A search added to or erased from the map needs a new snapshot (KAD_ERR_INVALID for an
+     * ID that is not mirrored); a list that outgrew the slabs takes one by itself. */
+    template <class InfoHashT>
+    void sync(const std::vector<InfoHashT>& changed) {
+        if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::sync before snapshot");
+        std::vector<uint32_t> which;
+        for (const auto& id : changed) which.push_back(index_of(id_bytes(id)));
+        std::sort(which.begin(), which.end());
+        which.erase(std::unique(which.begin(), which.end()), which.end());
+        if (which.empty()) return;
+        std::vector<uint8_t> flags, nid, nfl;
+        std::vector<uint32_t> off(1, 0u);
+        uint32_t longest = 0;
+        auto it = map_->begin();
+        uint32_t at = 0;
+        for (uint32_t w : which) {
+            std::advance(it, w - at);
+            at = w;
+            if (it == map_->end() || std::memcmp(id_bytes(it->first), &ids_[(size_t)w * KAD_HASH_LEN], KAD_HASH_LEN) != 0)
+                throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
+            append(*it->second, flags, off, nid, nfl);
+            longest = std::max<uint32_t>(longest, off.back() - off[off.size() - 2]);
+        }
+        if (longest > cap_) {
+            snapshot(*map_, device_, std::max(longest, 2 * cap_));
+            return;
+        }
+        check(kad_searches_patch(ss_, (uint32_t)which.size(), which.data(), flags.data(), off.data(), nid.data(),
+                                 nfl.data()), "kad_searches_patch");
+    }
+
+    /* Dht::trySearchInsert's verdict for each candidate ID taken alone against the searches as mirrored: one
+     * kad_sr_try_insert_batch_host call. The host then runs insertNode on the searches [lb - back, lb + fwd) only
+     * (node.time, removeExpiredNode, the scheduler edit) and reports them to sync(). */
+    template <class InfoHashT>
+    std::vector<SearchInsertVerdict> trySearchInsertBatch(const InfoHashT* ids, size_t q) const {
+        std::vector<SearchInsertVerdict> out(q);
+        if (q == 0) return out;
+        if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::trySearchInsertBatch before snapshot");
+        std::vector<uint8_t> cand(q * KAD_HASH_LEN), stop(q);
+        std::vector<uint32_t> lb(q), fwd(q), back(q);
+        for (size_t i = 0; i < q; i++) std::memcpy(&cand[i * KAD_HASH_LEN], id_bytes(ids[i]), KAD_HASH_LEN);
+        check(kad_sr_try_insert_batch_host(ss_, cand.data(), (uint32_t)q, lb.data(), fwd.data(), back.data(),
+                                           stop.data()), "kad_sr_try_insert_batch_host");
+        for (size_t i = 0; i < q; i++) out[i] = SearchInsertVerdict{lb[i], fwd[i], back[i], stop[i]};
+        return out;
+    }
+
+    size_t size() const { return ids_.size() / KAD_HASH_LEN; }
+    uint32_t cap() const { return cap_; }
+    const kad_searches* handle() const { return ss_; }
+
+private:
+    template <class SearchT>
+    static void append(const SearchT& s, std::vector<uint8_t>& flags, std::vector<uint32_t>& off,
+                       std::vector<uint8_t>& nid, std::vector<uint8_t>& nfl) {
+        flags.push_back(s.expired ? (uint8_t)KAD_SR_EXPIRED : (uint8_t)0);
+        for (const auto& sn : s.nodes) {
+            nid.insert(nid.end(), id_bytes(sn.node->id), id_bytes(sn.node->id) + KAD_HASH_LEN);
+            nfl.push_back(sn.isBad() ? (uint8_t)KAD_SN_BAD : (uint8_t)0);
+        }
+        off.push_back((uint32_t)nfl.size());
+    }
+    uint32_t index_of(const uint8_t* id) const {
+        size_t lo = 0, hi = size();
+        while (lo < hi) {
+            const size_t mid = (lo + hi) / 2;
+            if (std::memcmp(&ids_[mid * KAD_HASH_LEN], id, KAD_HASH_LEN) < 0) lo = mid + 1; else hi = mid;
+        }
+        if (lo == size() || std::memcmp(&ids_[lo * KAD_HASH_LEN], id, KAD_HASH_LEN) != 0)
+            throw Error(KAD_ERR_INVALID, "search not in the mirrored snapshot (snapshot again)");
+        return (uint32_t)lo;
+    }
+    void reset() {
+        if (ss_) kad_searches_destroy(ss_);
+        ss_ = nullptr;
+    }
+    void swap(SearchesMirror& o) {
+        std::swap(ss_, o.ss_);
+        std::swap(map_, o.map_);
+        ids_.swap(o.ids_);
+        std::swap(device_, o.device_);
+        std::swap(cap_, o.cap_);
+    }
+
+    kad_searches* ss_ = nullptr;
+    const SearchMapT* map_ = nullptr;
+    std::vector<uint8_t> ids_;  // the mirrored search IDs, ascending
+    int device_ = 0;
+    uint32_t cap_ = 0;
+};
+
+/* DhtMirror's search map when the Dht's searches are not mirrored. */
+struct NoSearchMap {};
+
 /* Dht-level accessor over both families: findClosestNodes(id, af, count)
  * = buckets(af).findClosestNodes(id, scheduler.time(), count) (dht.h:437-438; call sites dht.cpp:3196-3217).
  * `now` comes from the mirror's clock: steady_clock::now() by default, or the Dht scheduler's time
  * (setClock([&]{ return scheduler.time(); })). */
-template <class RoutingTableT, class Clock = std::chrono::steady_clock>
+template <class RoutingTableT, class Clock = std::chrono::steady_clock, class SearchMapT = NoSearchMap>
 class DhtMirror {
 public:
     using NodePtr = typename RoutingTableMirror<RoutingTableT>::NodePtr;
@@ -766,12 +908,28 @@ public:
                                                bool is_bootstrap) const {
         return buckets(af).onNewNodeBatch(ids, q, myid, clock_(), is_bootstrap);
     }
+    /* Dht::trySearchInsert's verdicts for the candidates of one family (SearchesMirror::trySearchInsertBatch), after
+     * snapshotSearches; syncSearches(af, changed) reports the searches the host's inserts changed. */
+    void snapshotSearches(const SearchMapT& searches4, const SearchMapT& searches6, int device = 0) {
+        s4_.snapshot(searches4, device);
+        s6_.snapshot(searches6, device);
+    }
+    template <class InfoHashT>
+    std::vector<SearchInsertVerdict> trySearchInsertBatch(const InfoHashT* ids, size_t q, sa_family_t af) const {
+        return searches(af).trySearchInsertBatch(ids, q);
+    }
+    template <class InfoHashT>
+    void syncSearches(sa_family_t af, const std::vector<InfoHashT>& changed) { searches(af).sync(changed); }
     /* Dht::buckets(af) (dht.h:437-438) */
     const RoutingTableMirror<RoutingTableT>& buckets(sa_family_t af) const { return af == AF_INET ? v4_ : v6_; }
     RoutingTableMirror<RoutingTableT>& buckets(sa_family_t af) { return af == AF_INET ? v4_ : v6_; }
+    /* Dht::searches(af) */
+    const SearchesMirror<SearchMapT>& searches(sa_family_t af) const { return af == AF_INET ? s4_ : s6_; }
+    SearchesMirror<SearchMapT>& searches(sa_family_t af) { return af == AF_INET ? s4_ : s6_; }
 
 private:
     RoutingTableMirror<RoutingTableT> v4_, v6_;
+    SearchesMirror<SearchMapT> s4_, s6_;
     std::function<time_point()> clock_;
 };
 

@@ -38,6 +38,8 @@ KAD_OP_REMOVE, KAD_OP_REPLACE, KAD_OP_INSERT, KAD_OP_SPLIT = 1, 2, 3, 4
 KAD_RESP_FAR, KAD_RESP_FAR4, KAD_RESP_FAR6 = 1, 1, 2
 KAD_NN_NONE, KAD_NN_KNOWN, KAD_NN_REPLACE, KAD_NN_INSERT, KAD_NN_SPLIT, KAD_NN_FULL = 0, 1, 2, 3, 4, 5
 KAD_NN_KIND_MASK, KAD_NN_MYBUCKET, KAD_NN_BOOTSTRAP = 0x0F, 0x10, 1
+KAD_SR_EXPIRED, KAD_SN_BAD = 0x01, 0x01
+KAD_SR_STOP_END, KAD_SR_STOP_KNOWN, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED = 0, 1, 2, 3
 
 
 def row_words(count: int) -> int:
@@ -134,6 +136,14 @@ SIGNATURES = {
     "kad_rt_responsible_batch_host": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P]),
     "kad_rt_triage_batch": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
     "kad_rt_triage_batch_host": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    "kad_search_trim": (C.c_int, [C.c_uint32, _P, C.c_uint32, _P, _P]),
+    "kad_searches_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]),
+    "kad_searches_patch": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "kad_searches_info": (C.c_int, [_P, _P, _P, _P]),
+    "kad_searches_export": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "kad_searches_destroy": (C.c_int, [_P]),
+    "kad_sr_try_insert_batch": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "kad_sr_try_insert_batch_host": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P]),
     "kad_rt_shard_batch": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
                                      _P, _P]),

@@ -1,0 +1,498 @@
+// kad_searches.hip — trySearchInsert verdicts over a device set of live searches.
+// Dht::onNewNode ends with trySearchInsert(node) (dht.cpp:816-849): lower_bound(node->id) in the family's
+// std::map<InfoHash, Sp<Search>>, then Search::insertNode (dht.cpp:961-1047) forwards and backwards until the first
+// search that refuses. On a node with many live searches nearly every candidate is refused by both neighbours; the
+// verdict of a whole tick is one launch here, and the host touches only the searches that accept.
+//
+// Layout, one family's set of S searches with a slab of `cap` members each:
+//   rec    S x 64 bytes  the probe record (kad_searches_plan.h): search ID, threshold ID entry[t-1], n, t, full and
+//                        expired bits. A probe of a search is this one line.
+//   skey   S x u64       (sets of up to LDS_KEYS searches) the search IDs' top 64 bits, dense, staged in LDS for the
+//                        lower bound; ties on the key are resolved from the records' tails
+//   rdx    2^B + 1 words (larger sets; B = ceil(log2 S), at most 24): the lower bound of every B-bit key prefix. The
+//                        binary search then runs over the one or two records of the candidate's prefix, which are the
+//                        neighbours the walks read anyway, instead of log2 S dependent probes of a key array
+//   mkey   S x cap x u64, mtail S x cap x 3 words, mflag S x cap bytes: the members. Read only when a candidate passes
+//                        the threshold, when the search is not full, or when members lie past the trim position.
+// One lane per candidate. A refused candidate costs the lower-bound probes plus the two records beside lb. A walk
+// over a run of accepting searches is serial in its lane (no wave-cooperative path).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/kadgpu.h"
+#include "kad_searches_plan.h"
+
+namespace kadgpu_internal {
+int set_error(int code, const char* msg);
+}  // namespace kadgpu_internal
+
+struct kad_searches {
+    int device = 0;
+    uint32_t S = 0, cap = 0;
+    uint32_t* rec = nullptr;
+    uint64_t* skey = nullptr;
+    uint64_t* mkey = nullptr;
+    uint32_t* mtail = nullptr;
+    uint8_t* mflag = nullptr;
+    uint32_t* rdx = nullptr;
+    uint32_t rshift = 0;  // 64 - B
+    uint64_t bytes = 0;
+    std::vector<uint8_t> h_ids;  // S x 20: a patch checks its lists against the search IDs
+};
+
+namespace {
+
+using kadgpu_internal::set_error;
+using kadplan::SREC_BITS;
+using kadplan::SREC_EXPIRED;
+using kadplan::SREC_FULL;
+using kadplan::SREC_N;
+using kadplan::SREC_T;
+using kadplan::SREC_THR;
+using kadplan::SREC_WORDS;
+
+constexpr int BLOCK = 256;
+constexpr uint32_t LDS_KEYS = 4096;   // 32 KB of search keys per workgroup
+constexpr uint32_t MAX_GRID = 2048;   // grid-stride beyond: the LDS staging is paid per workgroup
+constexpr uint32_t ACCEPT = 0xFFu;
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+
+#define SR_HIP_TRY(expr)                                                                            \
+    do {                                                                                            \
+        hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess)                                                                       \
+            return set_error(KAD_ERR_HIP, (std::string(#expr " failed: ") + hipGetErrorString(e_)).c_str()); \
+    } while (0)
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() {
+        int cur;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+struct DevSearches {
+    const u32x4_t* rec;
+    const uint64_t* skey;
+    const uint64_t* mkey;
+    const uint32_t* mtail;
+    const uint32_t* rdx;
+    uint32_t S, cap, rshift;
+};
+
+struct Rec {
+    u32x4_t r0, r1, r2, r3;
+};
+
+__device__ __forceinline__ Rec load_rec(const DevSearches& D, uint32_t s) {
+    const u32x4_t* r = D.rec + 4ull * s;
+    return Rec{r[0], r[1], r[2], r[3]};
+}
+
+struct Cand {
+    uint64_t hi;
+    uint32_t t2, t3, t4;
+};
+
+__device__ __forceinline__ Cand load_cand(const uint8_t* ids, uint32_t i) {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(ids + 20ull * i);
+    const uint32_t w0 = __builtin_nontemporal_load(p), w1 = __builtin_nontemporal_load(p + 1),
+                   w2 = __builtin_nontemporal_load(p + 2), w3 = __builtin_nontemporal_load(p + 3),
+                   w4 = __builtin_nontemporal_load(p + 4);
+    Cand c;
+    c.hi = ((uint64_t)__builtin_bswap32(w0) << 32) | __builtin_bswap32(w1);
+    c.t2 = __builtin_bswap32(w2);
+    c.t3 = __builtin_bswap32(w3);
+    c.t4 = __builtin_bswap32(w4);
+    return c;
+}
+
+// (a2, a3, a4) < (b2, b3, b4) as 96-bit numbers
+__device__ __forceinline__ bool tail_less(uint32_t a2, uint32_t a3, uint32_t a4, uint32_t b2, uint32_t b3,
+                                          uint32_t b4) {
+    if (a2 != b2) return a2 < b2;
+    if (a3 != b3) return a3 < b3;
+    return a4 < b4;
+}
+
+// x among the members [a, e) of search s (e <= n <= cap): keys eight at a time, none predicated (an index past the
+// range is clamped to its last entry), a member's tail only when its key equals the candidate's.
+__device__ __forceinline__ bool member(const DevSearches& D, uint32_t s, uint32_t a, uint32_t e, const Cand& x) {
+    const uint64_t* mk = D.mkey + (uint64_t)s * D.cap;
+    const uint32_t* mt = D.mtail + 3ull * s * D.cap;
+    for (uint32_t c = a; c < e; c += 8) {
+        uint64_t k[8];
+#pragma unroll
+        for (uint32_t u = 0; u < 8; u++) k[u] = mk[min(c + u, e - 1u)];
+#pragma unroll
+        for (uint32_t u = 0; u < 8; u++) {
+            if (c + u < e && k[u] == x.hi) {
+                const uint32_t* tl = mt + 3ull * (c + u);
+                if (tl[0] == x.t2 && tl[1] == x.t3 && tl[2] == x.t4) return true;
+            }
+        }
+    }
+    return false;
+}
+
+// accept(s, x) with R = the record of s: ACCEPT, or the stop code of the refusal.
+__device__ __forceinline__ uint32_t probe(const DevSearches& D, uint32_t s, const Rec& R, const Cand& x) {
+    const u32x4_t r0 = R.r0, r1 = R.r1, r2 = R.r2, r3 = R.r3;
+    const uint64_t ihi = ((uint64_t)r0.y << 32) | r0.x;
+    const uint32_t n = r1.y, t = r2.w, bits = r3.x;
+    if (bits & SREC_FULL) {  // t >= KAD_SEARCH_NODES: the threshold entry[t-1] exists
+        const uint64_t thi = ((uint64_t)r1.w << 32) | r1.z;
+        // XOR distances to the search ID: the u64 key first, the 96-bit tail only on equality
+        const uint64_t dx = x.hi ^ ihi, dt = thi ^ ihi;
+        bool closer;
+        if (dx != dt) {
+            closer = dx < dt;
+        } else {
+            closer = tail_less(x.t2 ^ r0.z, x.t3 ^ r0.w, x.t4 ^ r1.x, r2.x ^ r0.z, r2.y ^ r0.w, r2.z ^ r1.x);
+        }
+        if (!closer) {
+            const bool is_thr = x.hi == thi && x.t2 == r2.x && x.t3 == r2.y && x.t4 == r2.z;
+            if (is_thr || (n > t && member(D, s, t, n, x))) return KAD_SR_STOP_KNOWN;
+            return (bits & SREC_EXPIRED) ? KAD_SR_STOP_FAR_EXPIRED : KAD_SR_STOP_FAR;
+        }
+        // strictly closer than entry[t-1]: only entries before it can have x's ID
+        return member(D, s, 0, t - 1u, x) ? KAD_SR_STOP_KNOWN : ACCEPT;
+    }
+    return (n && member(D, s, 0, n, x)) ? KAD_SR_STOP_KNOWN : ACCEPT;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(BLOCK) void try_insert_kernel(DevSearches D, const uint8_t* __restrict__ ids, uint32_t q,
+                                                           uint32_t* __restrict__ out_lb, uint32_t* __restrict__ out_fwd,
+                                                           uint32_t* __restrict__ out_back,
+                                                           uint8_t* __restrict__ out_stop) {
+    __shared__ uint64_t sk[LDS ? LDS_KEYS : 1];
+    if (LDS) {
+        for (uint32_t j = threadIdx.x; j < D.S; j += BLOCK) sk[j] = D.skey[j];
+        __syncthreads();
+    }
+    for (uint64_t i0 = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i0 < q; i0 += (uint64_t)gridDim.x * BLOCK) {
+        const uint32_t i = (uint32_t)i0;
+        uint32_t lb = 0, fwd = 0, back = 0, fstop = KAD_SR_STOP_END, bstop = KAD_SR_STOP_END;
+        if (D.S) {  // kernel-uniform
+            const Cand x = load_cand(ids, i);
+            // lower_bound over the 160-bit search IDs: the keys, a record's tail only on a key tie
+            uint32_t lo = 0, hi = D.S;
+            if (!LDS) {  // the searches of the candidate's key prefix
+                const uint32_t p = (uint32_t)(x.hi >> D.rshift);
+                lo = D.rdx[p];
+                hi = D.rdx[p + 1];
+            }
+            while (lo < hi) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                // large sets compare against the record itself: within a prefix the probed records are the
+                // neighbours the walks read next, and a dense key array would be one more dependent random line
+                const u32x4_t* r = D.rec + 4ull * mid;
+                u32x4_t r0 = {};
+                if (!LDS) r0 = r[0];
+                const uint64_t k = LDS ? sk[mid] : (((uint64_t)r0.y << 32) | r0.x);
+                bool less = k < x.hi;
+                if (k == x.hi) {
+                    if (LDS) r0 = r[0];
+                    less = tail_less(r0.z, r0.w, r[1].x, x.t2, x.t3, x.t4);
+                }
+                if (less)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            lb = lo;
+            // both neighbours' records in flight together: the common candidate is refused by each at once
+            Rec rf = load_rec(D, min(lb, D.S - 1u)), rb = load_rec(D, max(lb, 1u) - 1u);
+            for (uint32_t s = lb; s < D.S;) {  // insert forward (dht.cpp:826-836)
+                const uint32_t v = probe(D, s, rf, x);
+                if (v != ACCEPT) {
+                    fstop = v;
+                    break;
+                }
+                fwd++;
+                if (++s < D.S) rf = load_rec(D, s);
+            }
+            for (uint32_t s = lb; s > 0;) {  // insert backward (dht.cpp:837-847)
+                const uint32_t v = probe(D, --s, rb, x);
+                if (v != ACCEPT) {
+                    bstop = v;
+                    break;
+                }
+                back++;
+                if (s > 0) rb = load_rec(D, s - 1u);
+            }
+        }
+        if (out_lb) __builtin_nontemporal_store(lb, out_lb + i);
+        __builtin_nontemporal_store(fwd, out_fwd + i);
+        __builtin_nontemporal_store(back, out_back + i);
+        __builtin_nontemporal_store((uint8_t)(fstop | (bstop << 4)), out_stop + i);
+    }
+}
+
+int launch(const kad_searches* ss, const uint8_t* ids, uint32_t q, uint32_t* out_lb, uint32_t* out_fwd,
+           uint32_t* out_back, uint8_t* out_stop, hipStream_t s) {
+    const DevSearches D{reinterpret_cast<const u32x4_t*>(ss->rec), ss->skey, ss->mkey, ss->mtail, ss->rdx, ss->S, ss->cap,
+                        ss->rshift};
+    const uint32_t blocks = (q + BLOCK - 1) / BLOCK, grid = blocks < MAX_GRID ? blocks : MAX_GRID;
+    if (ss->S <= LDS_KEYS)
+        hipLaunchKernelGGL(try_insert_kernel<true>, dim3(grid), dim3(BLOCK), 0, s, D, ids, q, out_lb, out_fwd, out_back,
+                           out_stop);
+    else
+        hipLaunchKernelGGL(try_insert_kernel<false>, dim3(grid), dim3(BLOCK), 0, s, D, ids, q, out_lb, out_fwd,
+                           out_back, out_stop);
+    SR_HIP_TRY(hipGetLastError());
+    return KAD_OK;
+}
+
+void free_device(kad_searches* ss) {
+    if (ss->rec) (void)hipFree(ss->rec);
+    if (ss->skey) (void)hipFree(ss->skey);
+    if (ss->mkey) (void)hipFree(ss->mkey);
+    if (ss->mtail) (void)hipFree(ss->mtail);
+    if (ss->mflag) (void)hipFree(ss->mflag);
+    if (ss->rdx) (void)hipFree(ss->rdx);
+    ss->rdx = nullptr;
+    ss->rec = nullptr;
+    ss->skey = nullptr;
+    ss->mkey = nullptr;
+    ss->mtail = nullptr;
+    ss->mflag = nullptr;
+}
+
+int check_lists(uint32_t m, const uint8_t* flags, const uint32_t* off, const uint8_t* node_ids,
+                const uint8_t* node_flags) {
+    if (!off || (m && !flags)) return set_error(KAD_ERR_INVALID, "NULL argument");
+    if (m && off[m] > 0 && (!node_ids || !node_flags)) return set_error(KAD_ERR_INVALID, "NULL node arrays");
+    return KAD_OK;
+}
+
+void put_be32(uint8_t* p, uint32_t v) {
+    p[0] = (uint8_t)(v >> 24);
+    p[1] = (uint8_t)(v >> 16);
+    p[2] = (uint8_t)(v >> 8);
+    p[3] = (uint8_t)v;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kad_searches_create(kad_searches** out, int device, uint32_t S, uint32_t cap, const uint8_t* ids,
+                        const uint8_t* flags, const uint32_t* off, const uint8_t* node_ids, const uint8_t* node_flags) {
+    if (!out) return set_error(KAD_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (S && !ids) return set_error(KAD_ERR_INVALID, "NULL argument");
+    if (int rc = check_lists(S, flags, off, node_ids, node_flags)) return rc;
+    if (cap < KAD_SEARCH_NODES) return set_error(KAD_ERR_INVALID, "cap below KAD_SEARCH_NODES");
+    if ((uint64_t)S * cap >= 0x7FFFFFFFull) return set_error(KAD_ERR_INVALID, "search set too large");
+    std::string err;
+    if (int rc = kadplan::searches_check_ids(S, ids, err)) return set_error(rc, err.c_str());
+    kadplan::SearchesPlan plan;
+    if (int rc = kadplan::searches_plan(S, cap, ids, flags, off, node_ids, node_flags, plan, err))
+        return set_error(rc, err.c_str());
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        (void)hipGetLastError();
+        return set_error(KAD_ERR_NO_DEVICE, "no such device");
+    }
+    kad_searches* ss = new kad_searches;
+    ss->device = device;
+    ss->S = S;
+    ss->cap = cap;
+    if (S) ss->h_ids.assign(ids, ids + 20ull * S);
+    if (S == 0) {
+        *out = ss;
+        return KAD_OK;
+    }
+    DeviceGuard g(device);
+    std::vector<uint64_t> skey(S);
+    for (uint32_t s = 0; s < S; s++) std::memcpy(&skey[s], plan.rec.data() + (size_t)s * SREC_WORDS, 8);
+    // the prefix directory of large sets: rdx[p] = the number of search keys whose top B bits are below p
+    std::vector<uint32_t> rdx;
+    if (S > LDS_KEYS) {
+        uint32_t B = 1;
+        while (B < 24 && (1u << B) < S) B++;
+        ss->rshift = 64 - B;
+        rdx.assign((1ull << B) + 1, 0u);
+        for (uint32_t s = 0; s < S; s++) rdx[(size_t)(skey[s] >> ss->rshift) + 1]++;
+        for (size_t p = 1; p < rdx.size(); p++) rdx[p] += rdx[p - 1];
+    }
+    const size_t b_rec = 64ull * S, b_skey = S > LDS_KEYS ? 0 : 8ull * S, b_mkey = 8ull * S * cap, b_mtail = 12ull * S * cap,
+                 b_mflag = (size_t)S * cap, b_rdx = 4ull * rdx.size();
+    if (hipMalloc((void**)&ss->rec, b_rec) != hipSuccess ||
+        (b_skey && hipMalloc((void**)&ss->skey, b_skey) != hipSuccess) ||
+        hipMalloc((void**)&ss->mkey, b_mkey) != hipSuccess || hipMalloc((void**)&ss->mtail, b_mtail) != hipSuccess ||
+        hipMalloc((void**)&ss->mflag, b_mflag) != hipSuccess ||
+        (b_rdx && hipMalloc((void**)&ss->rdx, b_rdx) != hipSuccess)) {
+        (void)hipGetLastError();
+        free_device(ss);
+        delete ss;
+        return set_error(KAD_ERR_NOMEM, "search set: out of device memory");
+    }
+    ss->bytes = b_rec + b_skey + b_mkey + b_mtail + b_mflag + b_rdx;
+    if (hipMemcpy(ss->rec, plan.rec.data(), b_rec, hipMemcpyHostToDevice) != hipSuccess ||
+        (b_skey && hipMemcpy(ss->skey, skey.data(), b_skey, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(ss->mkey, plan.mkey.data(), b_mkey, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(ss->mtail, plan.mtail.data(), b_mtail, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(ss->mflag, plan.mflag.data(), b_mflag, hipMemcpyHostToDevice) != hipSuccess ||
+        (b_rdx && hipMemcpy(ss->rdx, rdx.data(), b_rdx, hipMemcpyHostToDevice) != hipSuccess)) {
+        free_device(ss);
+        delete ss;
+        return set_error(KAD_ERR_HIP, "search set: upload failed");
+    }
+    *out = ss;
+    return KAD_OK;
+}
+
+int kad_searches_patch(kad_searches* ss, uint32_t m, const uint32_t* which, const uint8_t* flags, const uint32_t* off,
+                       const uint8_t* node_ids, const uint8_t* node_flags) {
+    if (!ss || (m && !which)) return set_error(KAD_ERR_INVALID, "NULL argument");
+    if (int rc = check_lists(m, flags, off, node_ids, node_flags)) return rc;
+    for (uint32_t k = 0; k < m; k++)
+        if (which[k] >= ss->S || (k && which[k] <= which[k - 1]))
+            return set_error(KAD_ERR_INVALID, "patched searches must be strictly ascending and below S");
+    if (m == 0) return KAD_OK;
+    std::vector<uint8_t> pid(20ull * m);
+    for (uint32_t k = 0; k < m; k++) std::memcpy(&pid[20ull * k], &ss->h_ids[20ull * which[k]], 20);
+    kadplan::SearchesPlan plan;
+    std::string err;
+    if (int rc = kadplan::searches_plan(m, ss->cap, pid.data(), flags, off, node_ids, node_flags, plan, err))
+        return set_error(rc, err.c_str());
+    DeviceGuard g(ss->device);
+    SR_HIP_TRY(hipDeviceSynchronize());  // queries enqueued before the call read the old set
+    const uint32_t cap = ss->cap;
+    // runs of consecutive searches travel as one copy per array
+    for (uint32_t a = 0; a < m;) {
+        uint32_t e = a + 1;
+        while (e < m && which[e] == which[e - 1] + 1) e++;
+        const uint64_t s0 = which[a], len = e - a;
+        SR_HIP_TRY(hipMemcpy(ss->rec + s0 * SREC_WORDS, plan.rec.data() + (size_t)a * SREC_WORDS, 64ull * len,
+                             hipMemcpyHostToDevice));
+        SR_HIP_TRY(hipMemcpy(ss->mkey + s0 * cap, plan.mkey.data() + (size_t)a * cap, 8ull * len * cap,
+                             hipMemcpyHostToDevice));
+        SR_HIP_TRY(hipMemcpy(ss->mtail + 3ull * s0 * cap, plan.mtail.data() + 3ull * a * cap, 12ull * len * cap,
+                             hipMemcpyHostToDevice));
+        SR_HIP_TRY(hipMemcpy(ss->mflag + s0 * cap, plan.mflag.data() + (size_t)a * cap, len * cap,
+                             hipMemcpyHostToDevice));
+        a = e;
+    }
+    return KAD_OK;
+}
+
+int kad_searches_info(const kad_searches* ss, uint32_t* S, uint32_t* cap, uint64_t* device_bytes) {
+    if (!ss) return set_error(KAD_ERR_INVALID, "NULL search set");
+    if (S) *S = ss->S;
+    if (cap) *cap = ss->cap;
+    if (device_bytes) *device_bytes = ss->bytes;
+    return KAD_OK;
+}
+
+int kad_searches_export(const kad_searches* ss, uint8_t* ids, uint8_t* flags, uint32_t* n, uint8_t* node_ids,
+                        uint8_t* node_flags, uint8_t* full, uint32_t* t) {
+    if (!ss) return set_error(KAD_ERR_INVALID, "NULL search set");
+    const uint32_t S = ss->S, cap = ss->cap;
+    if (S == 0) return KAD_OK;
+    DeviceGuard g(ss->device);
+    SR_HIP_TRY(hipDeviceSynchronize());
+    std::vector<uint32_t> rec((size_t)S * SREC_WORDS);
+    SR_HIP_TRY(hipMemcpy(rec.data(), ss->rec, 64ull * S, hipMemcpyDeviceToHost));
+    for (uint32_t s = 0; s < S; s++) {
+        const uint32_t* r = rec.data() + (size_t)s * SREC_WORDS;
+        if (ids) {
+            uint8_t* p = ids + 20ull * s;
+            put_be32(p, r[1]);
+            put_be32(p + 4, r[0]);
+            for (int w = 0; w < 3; w++) put_be32(p + 8 + 4 * w, r[2 + w]);
+        }
+        if (flags) flags[s] = (r[SREC_BITS] & SREC_EXPIRED) ? (uint8_t)KAD_SR_EXPIRED : 0;
+        if (n) n[s] = r[SREC_N];
+        if (full) full[s] = (r[SREC_BITS] & SREC_FULL) ? 1 : 0;
+        if (t) t[s] = r[SREC_T];
+    }
+    if (node_ids) {
+        const size_t e = (size_t)S * cap;
+        std::vector<uint64_t> mk(e);
+        std::vector<uint32_t> mt(3 * e);
+        SR_HIP_TRY(hipMemcpy(mk.data(), ss->mkey, 8ull * e, hipMemcpyDeviceToHost));
+        SR_HIP_TRY(hipMemcpy(mt.data(), ss->mtail, 12ull * e, hipMemcpyDeviceToHost));
+        for (size_t j = 0; j < e; j++) {
+            uint8_t* p = node_ids + 20ull * j;
+            put_be32(p, (uint32_t)(mk[j] >> 32));
+            put_be32(p + 4, (uint32_t)mk[j]);
+            for (int w = 0; w < 3; w++) put_be32(p + 8 + 4 * w, mt[3 * j + w]);
+        }
+    }
+    if (node_flags) SR_HIP_TRY(hipMemcpy(node_flags, ss->mflag, (size_t)S * cap, hipMemcpyDeviceToHost));
+    return KAD_OK;
+}
+
+int kad_searches_destroy(kad_searches* ss) {
+    if (!ss) return KAD_OK;
+    if (ss->S) {
+        DeviceGuard g(ss->device);
+        (void)hipDeviceSynchronize();
+        free_device(ss);
+    }
+    delete ss;
+    return KAD_OK;
+}
+
+int kad_sr_try_insert_batch(const kad_searches* ss, const uint8_t* ids, uint32_t q, uint32_t* out_lb,
+                            uint32_t* out_fwd, uint32_t* out_back, uint8_t* out_stop, void* stream) {
+    if (!ss) return set_error(KAD_ERR_INVALID, "NULL search set");
+    if (!ids || !out_fwd || !out_back || !out_stop) return set_error(KAD_ERR_INVALID, "NULL buffer");
+    if (q == 0) return KAD_OK;
+    if (((uintptr_t)ids | (uintptr_t)out_lb | (uintptr_t)out_fwd | (uintptr_t)out_back) & 3)
+        return set_error(KAD_ERR_INVALID, "device buffers must be 4-byte aligned");
+    DeviceGuard g(ss->device);
+    return launch(ss, ids, q, out_lb, out_fwd, out_back, out_stop, (hipStream_t)stream);
+}
+
+int kad_sr_try_insert_batch_host(const kad_searches* ss, const uint8_t* ids, uint32_t q, uint32_t* out_lb,
+                                 uint32_t* out_fwd, uint32_t* out_back, uint8_t* out_stop) {
+    if (!ss) return set_error(KAD_ERR_INVALID, "NULL search set");
+    if (!ids || !out_fwd || !out_back || !out_stop) return set_error(KAD_ERR_INVALID, "NULL buffer");
+    if (q == 0) return KAD_OK;
+    DeviceGuard g(ss->device);
+    // one allocation: ids, then the lb, fwd and back words, then the stop bytes
+    uint8_t* buf = nullptr;
+    hipStream_t s = nullptr;
+    auto done = [&](int r) {
+        if (s) (void)hipStreamDestroy(s);
+        if (buf) (void)hipFree(buf);
+        return r;
+    };
+    const size_t o_lb = 20ull * q, o_fwd = o_lb + 4ull * q, o_back = o_fwd + 4ull * q, o_stop = o_back + 4ull * q;
+    if (hipMalloc((void**)&buf, o_stop + q) != hipSuccess) {
+        (void)hipGetLastError();
+        return done(set_error(KAD_ERR_NOMEM, "try_insert host batch: out of device memory"));
+    }
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, "try_insert host batch: no stream"));
+    if (hipMemcpyAsync(buf, ids, 20ull * q, hipMemcpyHostToDevice, s) != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, "try_insert host batch: H2D failed"));
+    int rc = launch(ss, buf, q, (uint32_t*)(buf + o_lb), (uint32_t*)(buf + o_fwd), (uint32_t*)(buf + o_back),
+                    buf + o_stop, s);
+    if (rc == KAD_OK &&
+        ((out_lb && hipMemcpyAsync(out_lb, buf + o_lb, 4ull * q, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+         hipMemcpyAsync(out_fwd, buf + o_fwd, 4ull * q, hipMemcpyDeviceToHost, s) != hipSuccess ||
+         hipMemcpyAsync(out_back, buf + o_back, 4ull * q, hipMemcpyDeviceToHost, s) != hipSuccess ||
+         hipMemcpyAsync(out_stop, buf + o_stop, q, hipMemcpyDeviceToHost, s) != hipSuccess))
+        rc = set_error(KAD_ERR_HIP, "try_insert host batch: D2H failed");
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rc == KAD_OK && e != hipSuccess)
+        rc = set_error(KAD_ERR_HIP, (std::string("try_insert host batch: ") + hipGetErrorString(e)).c_str());
+    return done(rc);
+}
+
+}  // extern "C"

@@ -1,0 +1,40 @@
+// Host plan of a device search set (kad_searches_create / kad_searches_patch): the lists of one
+// family's live searches in CSR form checked and turned into the fixed slabs and the 64-byte probe records the
+// verdict kernel reads. Host-only C++ (no HIP), so that the CPU sanitizer build (tests/cpp/searches_plan_san.cpp)
+// runs it alone.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace kadplan {
+
+// One search's probe record, 16 words (one 64-byte line):
+//   0-1 search ID key (top 64 bits, one native u64)   2-4 search ID tail (three big-endian words as numbers)
+//   5   n (list length)                               6-7 threshold ID key, 8-10 its tail (entry[t-1]; 0 for t == 0)
+//   11  t (trim position)                             12  SREC_FULL | SREC_EXPIRED           13-15 zero
+constexpr uint32_t SREC_WORDS = 16, SREC_N = 5, SREC_THR = 6, SREC_T = 11, SREC_BITS = 12;
+constexpr uint32_t SREC_FULL = 1u, SREC_EXPIRED = 2u;
+
+struct SearchesPlan {
+    std::vector<uint32_t> rec;    // m x SREC_WORDS
+    std::vector<uint64_t> mkey;   // m x cap member keys (top 64 bits of the node ID), zero past n
+    std::vector<uint32_t> mtail;  // m x cap x 3 member tails
+    std::vector<uint8_t> mflag;   // m x cap member flag bytes
+};
+
+// Step 2 of Search::insertNode (dht.cpp:989-1007) on the flag bytes of a list of n entries: whether the search is
+// full and the trim position t <= n.
+void search_trim(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t* full, uint32_t* t);
+
+// S search IDs (20 B each) strictly ascending as 160-bit numbers: KAD_OK or KAD_ERR_INVALID with `err` set.
+int searches_check_ids(uint32_t S, const uint8_t* ids, std::string& err);
+
+// The slabs and records of m searches. ids: m x 20 B, the ID of each listed search; flags: m bytes; off: m + 1 CSR
+// offsets into node_ids (20 B each) / node_flags. Checked in this order: offsets not ascending or a list not strictly
+// ascending in XOR distance to its search ID (KAD_ERR_INVALID), then a list longer than cap (KAD_ERR_UNSUPPORTED).
+int searches_plan(uint32_t m, uint32_t cap, const uint8_t* ids, const uint8_t* flags, const uint32_t* off,
+                  const uint8_t* node_ids, const uint8_t* node_flags, SearchesPlan& out, std::string& err);
+
+}  // namespace kadplan
