@@ -252,6 +252,60 @@ int kad_table_export(const kad_table* t, uint8_t* ids, uint8_t* status, uint8_t*
 #define KAD_LINESET_DIR 12u   /* bucket directory: first node (bit 31: wide), good mask */
 int kad_table_export_lines(const kad_table* t, uint32_t set, void* out, uint64_t* bytes);
 
+/* ---- whole-table sweep (Dht::getNodesStats dht.cpp:2470-2495, Dht::expireBuckets dht.cpp:942-956) ---- */
+/* One read-only streaming pass over the table's status snapshot (refresh it to `now` first, as before queries) and
+ * its bucket directory: the counts getNodesStats walks the lists for, and what expireBuckets would remove.
+ *   expired_nodes    the nodes with KAD_STATUS_EXPIRED in ascending index order (bucket order, then list order),
+ *                    each plus index_base as every node output of this ABI (subtract it for KAD_OP_REMOVE's operand)
+ *   changed_buckets  the plain indices of the buckets holding at least one such node, ascending: the buckets
+ *                    expireBuckets calls sendCachedPing for (:953-954)
+ * Both lists are deterministic (the same table gives the same bytes). Either may be NULL with cap 0 (NULL with a
+ * non-zero cap: KAD_ERR_INVALID). A list holds only its first `cap` entries and nothing is written at or beyond
+ * `cap`; totals always carries the true counts, so an overflow shows as totals.expired > cap_nodes.
+ * Any table shape: split-policy, uniform and shard tables, buckets of any width, empty buckets, n_buckets == 0
+ * (NodeCache-only: the node counts, no buckets), n_nodes == 0. getNodesStats' `cached` (Bucket::cached, a host
+ * pointer per bucket) and bucketMaintenance's Bucket::time stay with the host.
+ * Device pointers (4-byte aligned); enqueues on `stream` and does not synchronise. A const query whose partial
+ * counts live in a stream-ordered allocation of the call's own: concurrent sweeps of one table on distinct streams
+ * are safe. Checked in this order, before any device work: NULL table, NULL totals, unknown flag bits, a NULL list
+ * with a non-zero cap, KAD_SWEEP_INCOMING on a table without kad_table_set_times (all KAD_ERR_INVALID). */
+#define KAD_SWEEP_INCOMING 1u   /* also count getNodesStats' `incoming` (reads the uploaded times) */
+typedef struct kad_sweep_totals {
+    uint32_t good;            /* status has KAD_STATUS_GOOD                     (dht.cpp:2476-2477) */
+    uint32_t dubious;         /* neither GOOD nor EXPIRED                       (:2480-2481)        */
+    uint32_t expired;         /* status has KAD_STATUS_EXPIRED: what expireBuckets removes (:947)   */
+    uint32_t incoming;        /* GOOD and time > reply_time (:2478-2479); 0 without the flag        */
+    uint32_t changed_buckets; /* buckets holding at least one EXPIRED node (:953-954)               */
+    uint32_t empty_buckets;   /* buckets without nodes                                              */
+    uint32_t flags;           /* the flags this sweep ran with                                      */
+    uint32_t reserved;        /* 0 */
+} kad_sweep_totals;
+int kad_table_sweep(const kad_table* t, uint32_t flags, kad_sweep_totals* totals, uint32_t* expired_nodes,
+                    uint32_t cap_nodes, uint32_t* changed_buckets, uint32_t cap_buckets, void* stream);
+/* kad_table_sweep on host buffers, synchronous, ordered after every change made to the table before the call; device
+ * buffers and a stream of the call's own. The outputs are written only when the call succeeds. */
+int kad_table_sweep_host(const kad_table* t, uint32_t flags, kad_sweep_totals* totals, uint32_t* expired_nodes,
+                         uint32_t cap_nodes, uint32_t* changed_buckets, uint32_t cap_buckets);
+/* Dht::expireBuckets on the device copy: removes every KAD_STATUS_EXPIRED node of the status snapshot. The table
+ * that results is the one kad_table_apply gives for one KAD_OP_REMOVE per expired node in ascending order (layout,
+ * directory, masks, good counts, line sets; KAD_TABLE_SORTED cleared), with one difference: the node times of
+ * kad_table_set_times and the wire records of kad_table_set_addrs are gathered through the remap on the device and
+ * stay attached, so kad_table_refresh_status and kad_buffer_nodes_batch work without a new upload (the deadlines are
+ * invalidated: the next refresh re-derives every node, as after kad_table_set_times).
+ *   remap            host or device, old n entries, may be NULL: as kad_table_apply
+ *   removed          host, cap_removed words (may be NULL with cap 0): the sweep's expired_nodes before the removal
+ *                    (old indices plus index_base), its first cap_removed entries; *n_removed (may be NULL) the count
+ *   changed_buckets  host, likewise: the sweep's changed_buckets; *n_changed the count
+ * No expired node: the table is untouched (same device arrays, line sets and flags), remap is the identity. Needs a
+ * RoutingTable (n_buckets > 0; KAD_ERR_INVALID otherwise, as kad_table_apply). A failure leaves the table as it was,
+ * times and wire records included, and writes no output. Synchronous.
+ * Memory the call keeps: the table holds a pinned host buffer for the read-back of the two lists (4 bytes per removed
+ * node and changed bucket of the largest call so far, freed with the table); the sweep's partial counts and this call's
+ * device lists come from a memory pool of the engine's own per device, which lives as long as the process and keeps
+ * what it is given back, up to 32 MB after a kad_table_expire that took more (the rest is returned to the driver). */
+int kad_table_expire(kad_table* t, uint32_t* remap, uint32_t* removed, uint32_t cap_removed, uint32_t* n_removed,
+                     uint32_t* changed_buckets, uint32_t cap_buckets, uint32_t* n_changed);
+
 /* ---- queries: RoutingTable::findClosestNodes ---------------------------- */
 /* Batched RoutingTable::findClosestNodes(target, now, count) (routing_table.cpp:67-111)
  * on the table's status snapshot. Device pointers:

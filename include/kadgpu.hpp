@@ -130,6 +130,13 @@ public:
                      "kad_rt_triage_batch_host");
     }
 
+    /* The whole-table sweep on host buffers (kad_table_sweep_host): the totals alone. */
+    kad_sweep_totals sweepTotals(uint32_t flags) const {
+        kad_sweep_totals tot;
+        check(kad_table_sweep_host(t_, flags, &tot, nullptr, 0, nullptr, 0), "kad_table_sweep_host");
+        return tot;
+    }
+
     /* Node liveness (kad_table_set_times / kad_table_patch_times) and the device-side isGood(now)
      * refresh (kad_table_refresh_status, incremental). */
     void setTimes(const std::vector<int64_t>& time_ns, const std::vector<int64_t>& reply_ns,
@@ -161,6 +168,20 @@ struct NewNodeVerdict {
     uint8_t verdict;
     uint32_t node;
     uint32_t bucket;
+};
+
+/* Dht::getNodesStats' counts (dht.cpp:2470-2495) plus the expired nodes (what expireBuckets would remove). `cached`
+ * (Bucket::cached) is host state and stays with the caller. */
+struct NodesStats {
+    unsigned good, dubious, incoming, expired;
+};
+
+/* What RoutingTableMirror::expireBuckets removed from the mirror: the nodes (erase them from the host's lists) and the
+ * indices of the buckets that held them (sendCachedPing for each, dht.cpp:953-954). */
+template <class NodePtrT>
+struct Expired {
+    std::vector<NodePtrT> removed;
+    std::vector<uint32_t> buckets;
 };
 
 /* time_point -> int64 nanoseconds of its clock, time_point::min()/max() -> INT64_MIN/MAX (Node::time and
@@ -332,6 +353,60 @@ public:
         for (size_t i = 0; i < q; i++) out[i] = NewNodeVerdict{verdict[i], node[i], bucket[i]};
         return out;
     }
+    /* Dht::getNodesStats (dht.cpp:2470-2495) over the mirrored table at `now`: one kad_table_sweep_host call with
+     * KAD_SWEEP_INCOMING, after the same refresh isTooFarBatch takes. No walk of the lists. */
+    template <class TimePoint>
+    NodesStats nodesStats(TimePoint now) const {
+        NodesStats st{0, 0, 0, 0};
+        if (nodes_.empty()) return st;
+        advance(to_ns(now));
+        const kad_sweep_totals tot = table_.sweepTotals(KAD_SWEEP_INCOMING);
+        st.good = tot.good;
+        st.dubious = tot.dubious;
+        st.incoming = tot.incoming;
+        st.expired = tot.expired;
+        return st;
+    }
+
+    /* Dht::expireBuckets (dht.cpp:942-956) on the mirror: every node whose isExpired() holds (as reported through
+     * nodeUpdated / syncTimes) leaves the device table in one kad_table_expire call, which keeps the node times and
+     * wire records of the others attached: no syncTimes() follows, unlike flush(). Returns the removed nodes and the
+     * buckets that held them; the host erases the former from its own lists and calls sendCachedPing for the latter.
+     * Pending un-flushed ops are flushed first. */
+    template <class TimePoint>
+    Expired<NodePtr> expireBuckets(TimePoint now) {
+        Expired<NodePtr> out;
+        flush(now);
+        if (nodes_.empty()) return out;
+        advance(to_ns(now));
+        std::vector<uint32_t> remap(nodes_.size()), removed(nodes_.size()), buckets(buckets_ ? buckets_ : 1);
+        uint32_t nr = 0, nb = 0;
+        check(kad_table_expire(table_.get(), remap.data(), removed.data(), (uint32_t)removed.size(), &nr, buckets.data(),
+                               buckets_, &nb),
+              "kad_table_expire");
+        if (nr == 0) return out;
+        kad_table_info inf;
+        check(kad_table_get_info(table_.get(), &inf), "kad_table_get_info");
+        out.removed.reserve(nr);
+        for (uint32_t j = 0; j < nr; j++) out.removed.push_back(nodes_[removed[j] - inf.index_base]);
+        out.buckets.assign(buckets.begin(), buckets.begin() + nb);
+        std::vector<NodePtr> next(inf.n_nodes);
+        for (size_t i = 0; i < nodes_.size(); i++)
+            if (remap[i] != KAD_NO_NODE) next[remap[i]] = nodes_[i];
+        nodes_.swap(next);
+        buckets_ = inf.n_buckets;
+        first_.assign((size_t)KAD_HASH_LEN * buckets_, 0);
+        off_.assign(buckets_ + 1, 0);
+        check(kad_table_export(table_.get(), nullptr, nullptr, buckets_ ? first_.data() : nullptr, off_.data()),
+              "kad_table_export");
+        reindex();
+        expire_calls_++;
+        return out;
+    }
+    /* Bookkeeping for tests: full liveness uploads (syncTimes) and expireBuckets calls that removed nodes. */
+    size_t syncTimesCalls() const { return sync_calls_; }
+    size_t expireCalls() const { return expire_calls_; }
+
     /* The mirrored node of a NewNodeVerdict's index. */
     const NodePtr& node(uint32_t index) const { return nodes_[index]; }
 
@@ -348,6 +423,7 @@ public:
             e[i] = nodes_[i]->isExpired() ? 1 : 0;
         }
         if (!nodes_.empty()) table_.setTimes(t, r, e);
+        sync_calls_++;
         updated_.clear();
         refresh_ = true;
     }
@@ -530,6 +606,7 @@ private:
     mutable std::vector<uint32_t> updated_;
     mutable int64_t now_ns_ = INT64_MIN;
     mutable bool refresh_ = false;
+    size_t sync_calls_ = 0, expire_calls_ = 0;
 };
 
 /* Device mirror of one NodeCache family map (node_cache.h:42-50: std::map<InfoHash, weak_ptr<Node>>). */
@@ -908,6 +985,18 @@ public:
                                                bool is_bootstrap) const {
         return buckets(af).onNewNodeBatch(ids, q, myid, clock_(), is_bootstrap);
     }
+    /* Dht::getNodesStats(af, good, dubious, cached, incoming) without `cached` (host state, Bucket::cached): the
+     * counts of one family at the mirror's clock; returns good + dubious as the reference does (dht.cpp:2494). */
+    unsigned getNodesStats(sa_family_t af, unsigned* good_return, unsigned* dubious_return,
+                           unsigned* incoming_return) const {
+        const NodesStats st = buckets(af).nodesStats(clock_());
+        if (good_return) *good_return = st.good;
+        if (dubious_return) *dubious_return = st.dubious;
+        if (incoming_return) *incoming_return = st.incoming;
+        return st.good + st.dubious;
+    }
+    /* Dht::expireBuckets(buckets(af)) (dht.cpp:942-956, run for both families by Dht::expire) on the mirror. */
+    Expired<NodePtr> expireBuckets(sa_family_t af) { return buckets(af).expireBuckets(clock_()); }
     /* Dht::trySearchInsert's verdicts for the candidates of one family (SearchesMirror::trySearchInsertBatch), after
      * snapshotSearches; syncSearches(af, changed) reports the searches the host's inserts changed. */
     void snapshotSearches(const SearchMapT& searches4, const SearchMapT& searches6, int device = 0) {

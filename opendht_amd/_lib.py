@@ -40,6 +40,7 @@ KAD_NN_NONE, KAD_NN_KNOWN, KAD_NN_REPLACE, KAD_NN_INSERT, KAD_NN_SPLIT, KAD_NN_F
 KAD_NN_KIND_MASK, KAD_NN_MYBUCKET, KAD_NN_BOOTSTRAP = 0x0F, 0x10, 1
 KAD_SR_EXPIRED, KAD_SN_BAD = 0x01, 0x01
 KAD_SR_STOP_END, KAD_SR_STOP_KNOWN, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED = 0, 1, 2, 3
+KAD_SWEEP_INCOMING = 1
 
 
 def row_words(count: int) -> int:
@@ -116,6 +117,9 @@ SIGNATURES = {
     "kad_table_apply": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P]),
     "kad_table_export": (C.c_int, [_P, _P, _P, _P, _P]),
     "kad_table_export_lines": (C.c_int, [_P, C.c_uint32, _P, _P]),
+    "kad_table_sweep": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _P]),
+    "kad_table_sweep_host": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32]),
+    "kad_table_expire": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
     "kad_nc_apply": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P]),
     "kad_table_set_times": (C.c_int, [_P, _P, _P, _P]),
     "kad_table_refresh_status": (C.c_int, [_P, C.c_int64, _P]),
@@ -240,6 +244,12 @@ class serve_stats(C.Structure):
         ("idle_us", C.c_uint32), ("last_polls", C.c_uint32), ("launches", C.c_uint64), ("requests", C.c_uint64),
         ("last_busy_ns", C.c_uint64),
     ]
+
+
+class sweep_totals(C.Structure):
+    """kad_sweep_totals"""
+    _fields_ = [(n, C.c_uint32) for n in ("good", "dubious", "expired", "incoming", "changed_buckets", "empty_buckets",
+                                          "flags", "reserved")]
 
 
 class refresh_diag(C.Structure):

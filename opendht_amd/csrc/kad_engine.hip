@@ -8135,6 +8135,8 @@ struct kad_table {
     float ls_ms[8] = {};
     hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
     hipStream_t bs = nullptr;       // line-set builds (ensure_lines): a non-blocking stream of the table's own
+    uint32_t* exp_pin = nullptr;    // pinned read-back of kad_table_expire's lists (grown on demand, kept)
+    size_t exp_pin_words = 0;
     ~kad_table() {
         if (bs) { (void)hipStreamSynchronize(bs); (void)hipStreamDestroy(bs); }
         for (hipStream_t x : ss)
@@ -8147,6 +8149,7 @@ struct kad_table {
                         (void*)rf_ctr, (void*)rf_blist, (void*)rf_nrange})
             if (p) (void)hipFree(p);
         if (rf_spin_host) (void)hipHostFree(rf_spin_host);
+        if (exp_pin) (void)hipHostFree(exp_pin);
     }
 };
 
@@ -10884,13 +10887,32 @@ int make_bucket_index(const std::vector<uint8_t>& h_first, uint32_t B, BucketInd
     return KAD_OK;
 }
 
-}  // namespace
+// Old node i's times and wire record to its new place remap[i] (kad_table_expire: removals keep the survivors'
+// order, so both sides of the copy are streams).
+__global__ void mirror_carry_kernel(const uint32_t* __restrict__ remap, uint32_t n0, const int64_t* __restrict__ time0,
+                                    const int64_t* __restrict__ reply0, const uint8_t* __restrict__ exp0,
+                                    int64_t* __restrict__ time1, int64_t* __restrict__ reply1, uint8_t* __restrict__ exp1,
+                                    const uint32_t* __restrict__ wrec0, uint32_t* __restrict__ wrec1, uint32_t rec_words) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n0) return;
+    const uint32_t j = remap[i];
+    if (j == NONE) return;
+    if (time0) {
+        time1[j] = time0[i];
+        reply1[j] = reply0[i];
+        exp1[j] = exp0[i];
+    }
+    if (wrec0)
+        for (uint32_t x = 0; x < rec_words; x++) wrec1[(size_t)rec_words * j + x] = wrec0[(size_t)rec_words * i + x];
+}
 
-extern "C" {
-
-int kad_table_apply(kad_table* t, const uint32_t* ops, uint32_t n_ops, const uint8_t* new_ids, const uint8_t* new_status,
-                    uint32_t n_new, uint32_t* remap, uint32_t* new_index) {
-    if (!t || (n_ops && !ops) || (n_new && (!new_ids || !new_status))) return set_err(KAD_ERR_INVALID, "NULL argument");
+// kad_table_apply; carry (kad_table_expire, removals only): the node times and wire records move with their nodes
+// instead of being dropped.
+// removals (with carry): n_ops old node indices plus rm_base, strictly ascending, in place of op rows.
+int table_apply(kad_table* t, const uint32_t* ops, uint32_t n_ops, const uint8_t* new_ids, const uint8_t* new_status,
+                uint32_t n_new, uint32_t* remap, uint32_t* new_index, bool carry, const uint32_t* removals = nullptr,
+                uint32_t rm_base = 0) {
+    if (!t || (n_ops && !ops && !removals) || (n_new && (!new_ids || !new_status))) return set_err(KAD_ERR_INVALID, "NULL argument");
     if (t->d.B == 0 || t->h_off.empty()) return set_err(KAD_ERR_INVALID, "the mirror needs a RoutingTable (buckets)");
     if ((uint64_t)t->d.n + n_new >= 0x7FFFFFFFull) return set_err(KAD_ERR_INVALID, "table too large");
     DeviceGuard g(t->device);
@@ -10925,8 +10947,9 @@ int kad_table_apply(kad_table* t, const uint32_t* ops, uint32_t n_ops, const uin
         return KAD_OK;
     };
     const bool wl_table = (d.flags & TF_WL) != 0;
-    int rc = kadplan::mirror_plan(off0, first0, n0, ops, n_ops, new_ids, n_new, wl_table ? (int)d.rshift : -1,
-                                  wl_table ? d.rbase >> d.rshift : 0, old_ids, plan, perr);
+    int rc = removals ? kadplan::mirror_plan_removals(off0, n0, removals, n_ops, rm_base, plan, perr)
+                      : kadplan::mirror_plan(off0, first0, n0, ops, n_ops, new_ids, n_new, wl_table ? (int)d.rshift : -1,
+                                             wl_table ? d.rbase >> d.rshift : 0, old_ids, plan, perr);
     if (rc) return perr.empty() ? rc : set_err(rc, "%s", perr.c_str());
     const bool structural = n_ops > 0;  // node indices move: the NodeCache radix no longer applies
     // window lines need every node inside its bucket's dyadic range
@@ -10960,18 +10983,35 @@ int kad_table_apply(kad_table* t, const uint32_t* ops, uint32_t n_ops, const uin
         (rc = dev_upload(&dnkey, nkey.data(), n_new, tmp, tmpb)) ||
         (rc = dev_upload(&dntail, ntail.data(), 3ull * n_new, tmp, tmpb)) ||
         (rc = dev_upload(&dnst, new_status, n_new, tmp, tmpb)) || (rc = dev_upload(&dnidx, nullptr, n_new, tmp, tmpb)) ||
-        (remap && (rc = dev_upload(&dremap, nullptr, n0, tmp, tmpb))))
+        ((remap || carry) && (rc = dev_upload(&dremap, nullptr, n0, tmp, tmpb))))
         return fail(rc);
+    // carried node state (kad_table_expire): new arrays filled through the remap before the commit
+    int64_t *time1 = nullptr, *reply1 = nullptr; uint8_t* exp1 = nullptr; uint32_t* wrec1 = nullptr;
+    const bool carry_times = carry && t->time_ns, carry_wrec = carry && t->wrec;
+    const uint32_t rec_words = (t->addr_len == KAD_ADDR4_LEN ? WREC4 : WREC6) / 4;
+    if (carry_times && ((rc = dev_upload(&time1, nullptr, n1, fresh, freshb)) ||
+                        (rc = dev_upload(&reply1, nullptr, n1, fresh, freshb)) ||
+                        (rc = dev_upload(&exp1, nullptr, n1, fresh, freshb))))
+        return fail(rc);
+    if (carry_wrec) {
+        if ((rc = dev_upload(&wrec1, nullptr, (size_t)rec_words * n1 + 4, fresh, freshb))) return fail(rc);
+        if (hipMemset(wrec1, 0, 4ull * ((size_t)rec_words * n1 + 4)) != hipSuccess)
+            return fail(set_err(KAD_ERR_HIP, "hipMemset failed"));
+    }
     if ((rc = dev_upload(&key1, nullptr, n1 + KEY_PAD, fresh, freshb)) ||
         (rc = dev_upload(&tail1, nullptr, 3ull * n1, fresh, freshb)) ||
         (rc = dev_upload(&st1, nullptr, n1, fresh, freshb)))
         return fail(rc);
     if (hipMemset(key1, 0xFF, 8ull * (n1 + KEY_PAD)) != hipSuccess || hipMemset(dnidx, 0xFF, 4ull * n_new) != hipSuccess ||
-        (remap && n0 && hipMemset(dremap, 0xFF, 4ull * n0) != hipSuccess))
+        (dremap && n0 && hipMemset(dremap, 0xFF, 4ull * n0) != hipSuccess))
         return fail(set_err(KAD_ERR_HIP, "hipMemset failed"));
     if (n1)
         hipLaunchKernelGGL(mirror_gather_kernel, dim3(grid_for(n1)), dim3(BLOCK), 0, 0, dseg, (uint32_t)segs.size(), dlist, n1,
                            d.key, d.tail, d.status, dnkey, dntail, dnst, key1, tail1, st1, dremap, dnidx);
+    if ((carry_times || carry_wrec) && n0)
+        hipLaunchKernelGGL(mirror_carry_kernel, dim3(grid_for(n0)), dim3(BLOCK), 0, 0, dremap, n0,
+                           carry_times ? t->time_ns : nullptr, t->reply_ns, t->expired, time1, reply1, exp1,
+                           carry_wrec ? t->wrec : nullptr, wrec1, rec_words);
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
         return fail(set_err(KAD_ERR_HIP, "mirror gather failed"));
     phase("upload + gather");
@@ -11030,9 +11070,10 @@ int kad_table_apply(kad_table* t, const uint32_t* ops, uint32_t n_ops, const uin
         release(t, t->ncl_mut); t->ncl_mut = nullptr; d.ncl = nullptr; d.flags &= ~TF_NCL;
         release(t, t->ncl32_mut); t->ncl32_mut = nullptr; d.ncl32 = nullptr; d.flags &= ~TF_NCL32;
     }
-    release(t, t->wrec); t->wrec = nullptr; t->addr_len = 0;
+    release(t, t->wrec); t->wrec = wrec1;
+    if (!wrec1) t->addr_len = 0;
     release(t, t->time_ns); release(t, t->reply_ns); release(t, t->expired);
-    t->time_ns = nullptr; t->reply_ns = nullptr; t->expired = nullptr;
+    t->time_ns = time1; t->reply_ns = reply1; t->expired = exp1;
     t->dl.invalidate();
     t->h_off.swap(off1);
     if (reshape) t->h_first.swap(first1);
@@ -11078,6 +11119,114 @@ int kad_table_apply(kad_table* t, const uint32_t* ops, uint32_t n_ops, const uin
     if (!(d.flags & TF_WL) && !t->gl_mut && !t->gl32_mut && (rc = setup_general_lines(t))) return rc;
     phase("general lines");
     reset_line_sets(t);
+    return KAD_OK;
+}
+
+}  // namespace
+
+#include "kad_sweep.h"
+
+extern "C" {
+
+int kad_table_apply(kad_table* t, const uint32_t* ops, uint32_t n_ops, const uint8_t* new_ids, const uint8_t* new_status,
+                    uint32_t n_new, uint32_t* remap, uint32_t* new_index) {
+    return table_apply(t, ops, n_ops, new_ids, new_status, n_new, remap, new_index, false);
+}
+
+int kad_table_expire(kad_table* t, uint32_t* remap, uint32_t* removed, uint32_t cap_removed, uint32_t* n_removed,
+                     uint32_t* changed_buckets, uint32_t cap_buckets, uint32_t* n_changed) {
+    if (!t || (!removed && cap_removed) || (!changed_buckets && cap_buckets))
+        return set_err(KAD_ERR_INVALID, "NULL argument");
+    if (t->d.B == 0 || t->h_off.empty()) return set_err(KAD_ERR_INVALID, "kad_table_expire needs a RoutingTable (buckets)");
+    DeviceGuard g(t->device);
+    const uint32_t n0 = t->d.n, base = t->d.index_base;
+    // KAD_DEBUG: the wall time of the call's own steps (kad_table_apply prints its phases in between)
+    const bool dbg = std::getenv("KAD_DEBUG") != nullptr;
+    auto tp = std::chrono::steady_clock::now();
+    auto phase = [&](const char* what) {
+        if (!dbg) return;
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "kad_table_expire %s: %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - tp).count());
+        tp = now;
+    };
+    // the sweep on the null stream (where kad_table_apply works), after the last asynchronous status refresh: the
+    // counts first, then lists of exactly the counted sizes
+    if (t->mut_async) HIP_TRY(hipStreamWaitEvent(nullptr, t->mut_ev, 0));
+    kad_sweep_totals* dtot = nullptr;
+    uint32_t* dlists = nullptr;
+    SweepTmp w;
+    hipMemPool_t pool = sweep_pool(t->device);
+    size_t pool_bytes = 0;
+    auto done = [&](int r) {
+        sweep_release(w, nullptr);
+        if (dtot) (void)hipFreeAsync(dtot, nullptr);
+        if (dlists) (void)hipFreeAsync(dlists, nullptr);
+        dtot = nullptr;
+        dlists = nullptr;
+        // a large expiry's lists do not stay parked in the pool for the life of the process
+        if (pool && pool_bytes > SWEEP_POOL_KEEP && hipStreamSynchronize(nullptr) == hipSuccess)
+            (void)hipMemPoolTrimTo(pool, SWEEP_POOL_KEEP);
+        return r;
+    };
+    // the totals and the lists come from the sweep's pool as well (no trip to the driver for the usual sizes)
+    auto pool_alloc = [&](void** p, size_t bytes) {
+        pool_bytes += bytes;
+        return pool ? hipMallocFromPoolAsync(p, bytes, pool, nullptr) : hipMallocAsync(p, bytes, nullptr);
+    };
+    if (pool_alloc((void**)&dtot, sizeof(kad_sweep_totals)) != hipSuccess) {
+        (void)hipGetLastError();
+        return done(set_err(KAD_ERR_NOMEM, "kad_table_expire: out of device memory"));
+    }
+    kad_sweep_totals tot;
+    int rc = sweep_count(t, 0, dtot, nullptr, w);
+    if (rc) return done(rc);
+    if (hipMemcpy(&tot, dtot, sizeof(tot), hipMemcpyDeviceToHost) != hipSuccess)
+        return done(set_err(KAD_ERR_HIP, "kad_table_expire: sweep failed"));
+    phase("sweep");
+    // The lists come back into pinned memory the table keeps: a pageable copy of some MB pins and unpins the
+    // destination on every call.
+    const size_t words = (size_t)tot.expired + tot.changed_buckets;
+    if (words > t->exp_pin_words) {
+        if (t->exp_pin) (void)hipHostFree(t->exp_pin);
+        t->exp_pin = nullptr;
+        t->exp_pin_words = 0;
+        const size_t want = words + words / 4 + 1024;
+        if (hipHostMalloc((void**)&t->exp_pin, 4 * want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            t->exp_pin = nullptr;
+            return done(set_err(KAD_ERR_NOMEM, "kad_table_expire: out of pinned host memory"));
+        }
+        t->exp_pin_words = want;
+    }
+    const uint32_t* nodes = t->exp_pin;
+    const uint32_t* buckets = t->exp_pin + tot.expired;
+    if (tot.expired) {
+        if (pool_alloc((void**)&dlists, 4ull * words) != hipSuccess) {
+            (void)hipGetLastError();
+            return done(set_err(KAD_ERR_NOMEM, "kad_table_expire: out of device memory"));
+        }
+        if ((rc = sweep_write(t, w, dlists, tot.expired, dlists + tot.expired, tot.changed_buckets, nullptr))) return done(rc);
+        if (hipMemcpyAsync(t->exp_pin, dlists, 4ull * words, hipMemcpyDeviceToHost, nullptr) != hipSuccess ||
+            hipStreamSynchronize(nullptr) != hipSuccess)
+            return done(set_err(KAD_ERR_HIP, "kad_table_expire: list copy failed"));
+    }
+    (void)done(KAD_OK);
+    phase("lists");
+    if (tot.expired == 0) {  // nothing to remove: the table stays as it is
+        if (remap && n0) {
+            std::vector<uint32_t> id(n0);
+            for (uint32_t i = 0; i < n0; i++) id[i] = i;
+            HIP_TRY(hipMemcpy(remap, id.data(), 4ull * n0, hipMemcpyDefault));
+        }
+    } else if ((rc = table_apply(t, nullptr, tot.expired, nullptr, nullptr, 0, remap, nullptr, true, nodes, base))) {
+        return rc;  // the sorted list is the plan's input as it is: no op rows
+    }
+    phase("apply");
+    for (uint32_t j = 0; j < std::min(tot.expired, cap_removed); j++) removed[j] = nodes[j];
+    for (uint32_t j = 0; j < std::min(tot.changed_buckets, cap_buckets); j++) changed_buckets[j] = buckets[j];
+    if (n_removed) *n_removed = tot.expired;
+    if (n_changed) *n_changed = tot.changed_buckets;
+    phase("outputs");
     return KAD_OK;
 }
 

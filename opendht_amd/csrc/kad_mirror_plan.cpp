@@ -46,7 +46,50 @@ struct PB {
     std::array<uint8_t, 20> first;
 };
 
+// The plan of n removals a[0], a[stride], ... (old node indices plus base, strictly ascending, all in the table): a
+// touched bucket becomes the handle list of its survivors, the untouched ones between them ranges of old nodes.
+void plan_removals(const std::vector<uint32_t>& off0, const uint32_t* a, size_t stride, uint32_t n, uint32_t base,
+                   MirrorPlan& out) {
+    const uint32_t B0 = (uint32_t)off0.size() - 1;
+    out = MirrorPlan{};
+    out.B1 = B0;
+    out.off1.resize(B0 + 1);
+    out.list.reserve(8ull * std::min<uint64_t>(n, B0));
+    uint32_t k = 0, acc = 0;
+    for (uint32_t o = 0; o < B0; o++) {
+        out.off1[o] = acc;
+        const uint32_t s = off0[o], e = off0[o + 1];
+        if (k < n && a[stride * k] - base < e) {  // a touched bucket: its survivors as a handle list
+            const uint32_t at = (uint32_t)out.list.size();
+            for (uint32_t i = s; i < e; i++) {
+                if (k < n && a[stride * k] - base == i) k++;
+                else out.list.push_back(i);
+            }
+            const uint32_t len = (uint32_t)out.list.size() - at;
+            if (len) out.segs.push_back(MirrorSeg{acc, at, len, 1});
+            acc += len;
+        } else if (e > s) {  // untouched: one range of old nodes, joined to the range before it
+            MirrorSeg* last = out.segs.empty() ? nullptr : &out.segs.back();
+            if (last && last->kind == 0 && last->src + last->len == s && last->start + last->len == acc) last->len += e - s;
+            else out.segs.push_back(MirrorSeg{acc, s, e - s, 0});
+            acc += e - s;
+        }
+    }
+    out.off1[B0] = acc;
+    out.n1 = acc;
+}
+
 }  // namespace
+
+int mirror_plan_removals(const std::vector<uint32_t>& off0, uint32_t n0, const uint32_t* nodes, uint32_t n, uint32_t base,
+                         MirrorPlan& out, std::string& err) {
+    if (off0.size() < 2) return fail(err, "the mirror needs a RoutingTable (buckets)");
+    for (uint32_t k = 0; k < n; k++)
+        if (nodes[k] - base >= n0 || nodes[k] < base || (k && nodes[k] <= nodes[k - 1]))
+            return fail(err, "removal %u: node %u out of range or not ascending", k, nodes[k]);
+    plan_removals(off0, nodes, 1, n, base, out);
+    return KAD_OK;
+}
 
 // Sparse plan: an origin bucket (a bucket of the table at the batch start) that an op touches gets the
 // list of its current buckets (splits add some); every other origin stays one untouched range. Host work
@@ -56,6 +99,15 @@ int mirror_plan(const std::vector<uint32_t>& off0, const uint8_t* first0, uint32
                 const OldIds& old_ids, MirrorPlan& out, std::string& err) {
     if (off0.size() < 2) return fail(err, "the mirror needs a RoutingTable (buckets)");
     const uint32_t B0 = (uint32_t)off0.size() - 1;
+    // Removals only, in strictly ascending node order (Dht::expireBuckets' sweep): the same plan from one walk of the
+    // directory beside the op list, without a map entry and a handle vector per touched bucket.
+    bool removals = n_ops > 0;
+    for (uint32_t k = 0; k < n_ops && removals; k++)
+        removals = ops[3ull * k] == KAD_OP_REMOVE && ops[3ull * k + 1] < n0 && (k == 0 || ops[3ull * k + 1] > ops[3ull * k - 2]);
+    if (removals) {
+        plan_removals(off0, ops + 1, 3, n_ops, 0, out);
+        return KAD_OK;
+    }
     std::unordered_map<uint32_t, std::vector<PB>> tb;  // touched origin -> its current buckets
     std::map<uint32_t, uint32_t> extra;                // split origin -> buckets its splits added
     uint32_t Bcur = B0;

@@ -38,4 +38,9 @@ int mirror_plan(const std::vector<uint32_t>& off0, const uint8_t* first0, uint32
                 uint32_t n_ops, const uint8_t* new_ids, uint32_t n_new, int range_shift, uint64_t range_pre0,
                 const OldIds& old_ids, MirrorPlan& out, std::string& err);
 
+// The plan of removals alone (kad_table_expire): nodes[0..n) are old node indices plus `base`, strictly ascending
+// (KAD_ERR_INVALID otherwise). Equal to mirror_plan's result for one KAD_OP_REMOVE row per node.
+int mirror_plan_removals(const std::vector<uint32_t>& off0, uint32_t n0, const uint32_t* nodes, uint32_t n, uint32_t base,
+                         MirrorPlan& out, std::string& err);
+
 }  // namespace kadplan

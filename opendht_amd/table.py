@@ -183,6 +183,73 @@ class DeviceTable:
         self.n, self.B = inf["n_nodes"], inf["n_buckets"]
         return out[:nid.shape[0]]
 
+    def sweep(self, incoming: bool = False, want_nodes: bool = True, want_buckets: bool = True, cap_nodes=None,
+              cap_buckets=None, stream=None, out=None):
+        """Dht::getNodesStats and the scan of Dht::expireBuckets in one device pass (kad_table_sweep) over the current
+        status snapshot. Returns a dict: `totals` (the kad_sweep_totals fields as ints), `expired_nodes` (int32 device
+        tensor view of uint32: the EXPIRED nodes ascending, plus index_base) and `changed_buckets` (int32 device tensor:
+        the buckets holding one), each cut to min(count, cap), or None when not wanted. cap_* default to n / B. out: a
+        (nodes, buckets) pair of int32 device tensors to write into (at least cap entries each). Waits for the
+        stream to read the totals."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        s = _stream_of(self, stream)
+        cn = (self.n if cap_nodes is None else int(cap_nodes)) if want_nodes else 0
+        cb = (self.B if cap_buckets is None else int(cap_buckets)) if want_buckets else 0
+        nodes, buckets = out if out is not None else (None, None)
+        if nodes is None and cn:
+            nodes = torch.empty((cn,), dtype=torch.int32, device=dev)
+        if buckets is None and cb:
+            buckets = torch.empty((cb,), dtype=torch.int32, device=dev)
+        tot = torch.empty((8,), dtype=torch.int32, device=dev)
+        check(lib().kad_table_sweep(self._h, _lib.KAD_SWEEP_INCOMING if incoming else 0, ptr(tot),
+                                    ptr(nodes) if cn else None, cn, ptr(buckets) if cb else None, cb, s),
+              "kad_table_sweep")
+        if stream is None:
+            torch.cuda.current_stream(dev).synchronize()
+        elif hasattr(stream, "synchronize"):
+            stream.synchronize()
+        else:
+            torch.cuda.ExternalStream(int(stream), device=dev).synchronize()
+        vals = tot.cpu().numpy().view(np.uint32)
+        totals = {f: int(vals[k]) for k, (f, _) in enumerate(_lib.sweep_totals._fields_)}
+        empty = torch.empty((0,), dtype=torch.int32, device=dev)
+        return {"totals": totals,
+                "expired_nodes": (nodes[:min(totals["expired"], cn)] if cn else empty) if want_nodes else None,
+                "changed_buckets": (buckets[:min(totals["changed_buckets"], cb)] if cb else empty) if want_buckets
+                else None}
+
+    def sweep_host(self, incoming: bool = False, want_nodes: bool = True, want_buckets: bool = True, cap_nodes=None,
+                   cap_buckets=None):
+        """sweep on host buffers, synchronous (kad_table_sweep_host): the same dict with numpy uint32 arrays."""
+        cn = (self.n if cap_nodes is None else int(cap_nodes)) if want_nodes else 0
+        cb = (self.B if cap_buckets is None else int(cap_buckets)) if want_buckets else 0
+        nodes = np.zeros(max(cn, 1), np.uint32)
+        buckets = np.zeros(max(cb, 1), np.uint32)
+        tot = _lib.sweep_totals()
+        check(lib().kad_table_sweep_host(self._h, _lib.KAD_SWEEP_INCOMING if incoming else 0, C.byref(tot),
+                                         ptr(nodes) if cn else None, cn, ptr(buckets) if cb else None, cb),
+              "kad_table_sweep_host")
+        totals = {f: int(getattr(tot, f)) for f, _ in tot._fields_}
+        return {"totals": totals,
+                "expired_nodes": nodes[:min(totals["expired"], cn)] if want_nodes else None,
+                "changed_buckets": buckets[:min(totals["changed_buckets"], cb)] if want_buckets else None}
+
+    def expire(self, remap=None):
+        """Dht::expireBuckets on the device copy (kad_table_expire): every KAD_STATUS_EXPIRED node leaves; node times
+        and wire records stay attached to the survivors. `remap` (device int32 tensor or host uint32 array, old n)
+        receives every old node's new index. Returns (removed, changed_buckets): host uint32 arrays with the old
+        indices (plus index_base) of the removed nodes and the buckets that held them."""
+        removed = np.empty(max(self.n, 1), np.uint32)  # not zeroed: only the first nr / nb entries are written and returned
+        buckets = np.empty(max(self.B, 1), np.uint32)
+        nr, nb = C.c_uint32(0), C.c_uint32(0)
+        check(lib().kad_table_expire(self._h, ptr(remap), ptr(removed), self.n, C.byref(nr), ptr(buckets), self.B,
+                                     C.byref(nb)), "kad_table_expire")
+        inf = self.info()
+        self.n, self.B = inf["n_nodes"], inf["n_buckets"]
+        return removed[:nr.value], buckets[:nb.value]
+
     def nc_apply(self, erase=None, ins_ids=None, ins_status=None):
         """NodeCache map mutations (kad_nc_apply) on a NodeCache-only table: erase the listed node indices,
         insert new IDs. Returns (remap (old n,) uint32, new_index (n_ins,) uint32), both host arrays."""
