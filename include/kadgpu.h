@@ -517,6 +517,51 @@ int kad_sr_try_insert_batch(const kad_searches* ss, const uint8_t* ids, uint32_t
 int kad_sr_try_insert_batch_host(const kad_searches* ss, const uint8_t* ids, uint32_t q, uint32_t* out_lb,
                                  uint32_t* out_fwd, uint32_t* out_back, uint8_t* out_stop);
 
+/* ---- Dht::refill over a set of live searches (dht.cpp:1647-1668) ---- */
+/* For each listed search s, against the snapshots `ss` and `nc` (one family's NodeCache as a KAD_TABLE_SORTED table):
+ *   1. row = getCachedNodes(s.id, af, KAD_SEARCH_NODES): the indices kad_nc_closest_batch(nc, s.id, 14) gives, in walk
+ *      order, each plus index_base; cnt their number.
+ *   2. cnt == 0: the search is untouched (:1652-1656).
+ *   3. otherwise s.insertNode(x_j, now, empty token) for j = 0 .. cnt-1 in order, x_j the ID of row[j], with node
+ *      identity = ID (dht.cpp:961-1047):
+ *        found   a member has x_j's ID: false, nothing changes (:972-984);
+ *        trim    t and full as kad_search_trim; full and t < n cuts the list to t entries even when the candidate is
+ *                then refused; full and insert position >= t refuses (:1009-1013);
+ *        insert  at the position found by the strict 160-bit XOR-distance compare, flag byte 0 (a getCachedNodes
+ *                result is not expired, and `candidate` is false);
+ *        flip    an expired search becomes live and nothing is popped by this call (:1026-1029);
+ *        pops    a live search pops from the back while more than 14 entries are not KAD_SN_BAD (:1031-1035);
+ *        erase   removeExpiredNode(now) after every insert (:1044-1045, dht.h:628-640): the entry with the greatest
+ *                index that carries KAD_SN_REMOVABLE goes.
+ *   4. the record and slab of s are rewritten: list, KAD_SR_EXPIRED, n, t, full and the threshold entry[t-1] are what
+ *      kad_searches_create derives from the new list, so verdicts and exports cannot tell a refilled set from a new one.
+ * KAD_SN_REMOVABLE = node->isExpired() && node->time + NODE_EXPIRE_TIME < now, evaluated by the host for the refill's
+ * `now`; it rides in the flag byte, which create, patch and export pass through unchanged. The searches of a batch
+ * are distinct, the NodeCache snapshot is not changed, and getCachedNodes returns no expired node, so node.time = now
+ * changes no test in another search: the batch gives the sequential result. node.time on the RoutingTable copy is
+ * reported by the host (kad_table_patch_times).
+ * A list may not outgrow its slab: a search whose list would hold more than cap entries after some insertNode of its
+ * row returns gets KAD_SR_REFILL_OVERFLOW, is left byte for byte as it was, and its inserted mask is 0 (row and cnt
+ * are still written); the host runs the walk from the row and creates the set again with a larger cap.
+ * Host arrays, synchronous; as kad_searches_patch towards queries (it first waits for all device work enqueued before
+ * the call). which: m search indices, strictly ascending, < S. out_rows: m x KAD_SEARCH_NODES, padded with KAD_NO_NODE,
+ * may be NULL; out_cnt m bytes; out_inserted m words of 16 bits, bit j = insertNode(row[j]) returned true; out_status m
+ * bytes. Checked in this order, before any device work: NULL ss / nc; NULL which / out_cnt / out_inserted / out_status
+ * with m > 0; which not strictly ascending or not < S (all KAD_ERR_INVALID); nc without KAD_TABLE_SORTED
+ * (KAD_ERR_NOT_SORTED); nc on another device than ss (KAD_ERR_INVALID); m == 0 (KAD_OK); then a set whose cap exceeds
+ * 64, the lanes of the wave that holds a list (KAD_ERR_UNSUPPORTED). Every failure reported before the refill kernel
+ * runs (these checks, out of host or device memory, a failed upload or launch) leaves the set unchanged; past it only a
+ * HIP error of the copy back remains (KAD_ERR_HIP: the device is then in error). One wave per
+ * search, one list entry per lane; the scratch is allocated per call. */
+#define KAD_SN_REMOVABLE 0x02u        /* node flag: removeExpiredNode(now) would erase this entry */
+#define KAD_SR_REFILL_OK 0u
+#define KAD_SR_REFILL_OVERFLOW 1u
+int kad_sr_refill(kad_searches* ss, const kad_table* nc, uint32_t m, const uint32_t* which, uint32_t* out_rows,
+                  uint8_t* out_cnt, uint16_t* out_inserted, uint8_t* out_status);
+/* Measurement aid (tools/refill_bench.py), not part of the refill interface: the device time of the refill kernel of
+ * the last kad_sr_refill on this set, in milliseconds, from two events the call records around it (0 before the first). */
+int kad_sr_refill_kernel_ms(const kad_searches* ss, float* out_ms);
+
 /* Per-query family select for NodeCache::getCachedNodes(id, sa_family, count) (node_cache.cpp:36-66:
  * cache_4 or cache_6 by family; Dht::refill asks the search's family, dht.cpp:1650): af[i] = 0 -> table4,
  * 1 -> table6 (KAD_TABLE_SORTED tables; either may be NULL = an empty map). Any count (as kad_nc_closest_batch).

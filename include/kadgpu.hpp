@@ -753,6 +753,14 @@ public:
                            std::vector<uint8_t>{(uint8_t)(n->isExpired() ? KAD_STATUS_EXPIRED : 0u)});
     }
     size_t size() const { return nodes_.size(); }
+    /* The device table and the node behind one of its indices (SearchesMirror::refillBatch). */
+    const DeviceTable& table() const { return table_; }
+    NodePtr nodeAt(uint32_t idx) const { return idx < nodes_.size() ? nodes_[idx].lock() : NodePtr(); }
+    /* A node of a device result was found dead or expired on the host: mark it on the device, as
+     * getCachedNodesBatch does. */
+    void markStale(const std::vector<uint32_t>& idx) const {
+        if (!idx.empty()) table_.patchStatus(idx, std::vector<uint8_t>(idx.size(), (uint8_t)KAD_STATUS_EXPIRED));
+    }
 
 private:
     static uint8_t status_of(const NodePtr& n) {
@@ -808,6 +816,18 @@ struct SearchInsertVerdict {
     uint8_t stop;
 };
 
+/* One search's Dht::refill on the device (SearchesMirror::refillBatch): the getCachedNodes result in walk order, bit j
+ * of inserted = insertNode(nodes[j], now) returned true on the device copy, and overflow = the device copy was not
+ * refilled (its list outgrew the slab, or a node of the row was found dead or expired on the host): the host's own
+ * insertNode loop over `nodes` stands, and the search is reported to sync(). The name follows KAD_SR_REFILL_OVERFLOW;
+ * read it as "handed back to the host", whichever of the two reasons applies. */
+template <class NodePtr>
+struct RefillResult {
+    std::vector<NodePtr> nodes;
+    uint16_t inserted;
+    bool overflow;  // handed back: the host's walk stands and sync() overwrites the device copy
+};
+
 /* Device mirror of one family's live searches (Dht::searches(af), dht.h) over a map shaped like
  * std::map<InfoHash, std::shared_ptr<Search>>. Reads of a search: id, expired, nodes[i].node->id, nodes[i].isBad().
  * The map must outlive the mirror or the next snapshot. */
@@ -828,12 +848,23 @@ public:
     }
 
     /* Snapshot every search of `map`. cap: slab entries per search, grown to the longest list. */
-    void snapshot(const SearchMapT& map, int device = 0, uint32_t cap = 32) {
+    void snapshot(const SearchMapT& map, int device = 0, uint32_t cap = 32) { snapshotAt(map, NoTime(), device, cap); }
+    /* The same with KAD_SN_REMOVABLE set on the entries removeExpiredNode(now) would erase (node->isExpired() &&
+     * node->time + Node::NODE_EXPIRE_TIME < now, dht.h:628-640): what refillBatch at `now` needs. Chosen only for a
+     * std::chrono time point: snapshot(map, 0, 14) with plain integers stays the overload above. */
+    template <class TimePoint, class = typename TimePoint::duration>
+    void snapshot(const SearchMapT& map, TimePoint now, int device = 0, uint32_t cap = 32) {
+        snapshotAt(map, At<TimePoint>{now}, device, cap);
+    }
+
+private:
+    template <class When>
+    void snapshotAt(const SearchMapT& map, const When& when, int device, uint32_t cap) {
         std::vector<uint8_t> ids, flags, nid, nfl;
         std::vector<uint32_t> off(1, 0u);
         for (const auto& kv : map) {
             ids.insert(ids.end(), id_bytes(kv.first), id_bytes(kv.first) + KAD_HASH_LEN);
-            append(*kv.second, flags, off, nid, nfl);
+            append(*kv.second, flags, off, nid, nfl, when);
             cap = std::max<uint32_t>(cap, off.back() - off[off.size() - 2]);
         }
         kad_searches* ss = nullptr;
@@ -845,13 +876,103 @@ public:
         ids_.swap(ids);
         device_ = device;
         cap_ = cap;
+        at_.assign(size(), when.ns());
     }
 
+public:
     /* The searches with these IDs changed their list or flags (the host's inserts, a node turning bad, expiry):
      * one kad_searches_patch. A search added to or erased from the map needs a new snapshot (KAD_ERR_INVALID for an
      * ID that is not mirrored); a list that outgrew the slabs takes one by itself. */
     template <class InfoHashT>
-    void sync(const std::vector<InfoHashT>& changed) {
+    void sync(const std::vector<InfoHashT>& changed) { syncAt(changed, NoTime()); }
+    /* The same with KAD_SN_REMOVABLE evaluated at `now` (see snapshot). */
+    template <class InfoHashT, class TimePoint, class = typename TimePoint::duration>
+    void sync(const std::vector<InfoHashT>& changed, TimePoint now) { syncAt(changed, At<TimePoint>{now}); }
+
+    /* Dht::refill (dht.cpp:1647-1668) of the searches `ids` (distinct, mirrored) from the NodeCache family mirror
+     * `nc` on the device: one kad_sr_refill. Searches whose KAD_SN_REMOVABLE bits at `now` differ from the mirrored
+     * ones are patched first. Results in the order of `ids`. The host then runs sr.insertNode(n, now) over every
+     * result's nodes on its own searches (the device copy already holds the outcome; a refused insert can still trim)
+     * and reports the searches with overflow set to sync(changed, now). nc must be on the mirror's device.
+     * Precondition: which bits "differ" is worked out from each member node's current isExpired() and time against
+     * the time the search was last uploaded at, so every change of those two fields of a node held by a mirrored
+     * search (setExpired, a reply, another search's insertNode writing node->time) must have been reported through
+     * sync(changed, now) before; a search whose members changed unreported may keep stale bits on the device. */
+    template <class NodeMapT, class InfoHashT, class TimePoint>
+    std::vector<RefillResult<typename NodeCacheFamilyMirror<NodeMapT>::NodePtr>>
+    refillBatch(const NodeCacheFamilyMirror<NodeMapT>& nc, const std::vector<InfoHashT>& ids, TimePoint now) {
+        typedef typename NodeCacheFamilyMirror<NodeMapT>::NodePtr NodePtr;
+        std::vector<RefillResult<NodePtr>> out(ids.size());
+        if (ids.empty()) return out;
+        if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::refillBatch before snapshot");
+        const uint32_t m = (uint32_t)ids.size();
+        std::vector<std::pair<uint32_t, uint32_t>> order(m);  // (search index, position in ids)
+        for (uint32_t i = 0; i < m; i++) order[i] = std::make_pair(index_of(id_bytes(ids[i])), i);
+        std::sort(order.begin(), order.end());
+        std::vector<uint32_t> which(m);
+        for (uint32_t k = 0; k < m; k++) {
+            if (k && order[k].first == order[k - 1].first)
+                throw Error(KAD_ERR_INVALID, "SearchesMirror::refillBatch: a search listed twice");
+            which[k] = order[k].first;
+        }
+        // the searches whose REMOVABLE bits moved since they were uploaded
+        const At<TimePoint> when{now};
+        std::vector<InfoHashT> moved;
+        {
+            auto it = map_->begin();
+            uint32_t at = 0;
+            for (uint32_t k = 0; k < m; k++) {
+                std::advance(it, which[k] - at);
+                at = which[k];
+                if (it == map_->end() || std::memcmp(id_bytes(it->first), &ids_[(size_t)at * KAD_HASH_LEN], KAD_HASH_LEN) != 0)
+                    throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
+                bool differ = false;
+                for (const auto& sn : it->second->nodes)
+                    differ = differ || when.removable(*sn.node) != (at_[at] != INT64_MIN && when.removableAt(*sn.node, at_[at]));
+                if (differ) moved.push_back(ids[order[k].second]);
+            }
+        }
+        if (!moved.empty()) syncAt(moved, when);
+        std::vector<uint32_t> rows((size_t)m * KAD_SEARCH_NODES);
+        std::vector<uint8_t> cnt(m), st(m);
+        std::vector<uint16_t> ins(m);
+        check(kad_sr_refill(ss_, nc.table().get(), m, which.data(), rows.data(), cnt.data(), ins.data(), st.data()),
+              "kad_sr_refill");
+        std::vector<uint32_t> stale;
+        for (uint32_t k = 0; k < m; k++) {
+            RefillResult<NodePtr>& r = out[order[k].second];
+            r.inserted = ins[k];
+            r.overflow = st[k] != KAD_SR_REFILL_OK;
+            bool ok = true;
+            for (uint32_t j = 0; j < cnt[k]; j++) {
+                const uint32_t x = rows[(size_t)k * KAD_SEARCH_NODES + j];
+                NodePtr n = nc.nodeAt(x);
+                if (!n || n->isExpired()) { stale.push_back(x); ok = false; continue; }
+                r.nodes.push_back(std::move(n));
+            }
+            if (!ok) r.overflow = true;  // the device walked over a node the host no longer takes
+            at_[which[k]] = when.ns();
+        }
+        if (!stale.empty()) {  // those rows again, exactly, on the host path; their searches go through sync()
+            std::sort(stale.begin(), stale.end());
+            stale.erase(std::unique(stale.begin(), stale.end()), stale.end());
+            nc.markStale(stale);
+            for (uint32_t k = 0; k < m; k++) {
+                RefillResult<NodePtr>& r = out[order[k].second];
+                if (r.nodes.size() != cnt[k]) {
+                    r.nodes = nc.getCachedNodes(ids[order[k].second], KAD_SEARCH_NODES);
+                    r.inserted = 0;
+                }
+            }
+        }
+        for (auto& r : out)
+            if (r.overflow) r.inserted = 0;
+        return out;
+    }
+
+private:
+    template <class InfoHashT, class When>
+    void syncAt(const std::vector<InfoHashT>& changed, const When& when) {
         if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::sync before snapshot");
         std::vector<uint32_t> which;
         for (const auto& id : changed) which.push_back(index_of(id_bytes(id)));
@@ -868,16 +989,19 @@ public:
             at = w;
             if (it == map_->end() || std::memcmp(id_bytes(it->first), &ids_[(size_t)w * KAD_HASH_LEN], KAD_HASH_LEN) != 0)
                 throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
-            append(*it->second, flags, off, nid, nfl);
+            append(*it->second, flags, off, nid, nfl, when);
             longest = std::max<uint32_t>(longest, off.back() - off[off.size() - 2]);
         }
         if (longest > cap_) {
-            snapshot(*map_, device_, std::max(longest, 2 * cap_));
+            snapshotAt(*map_, when, device_, std::max(longest, 2 * cap_));
             return;
         }
         check(kad_searches_patch(ss_, (uint32_t)which.size(), which.data(), flags.data(), off.data(), nid.data(),
                                  nfl.data()), "kad_searches_patch");
+        for (uint32_t w : which) at_[w] = when.ns();
     }
+
+public:
 
     /* Dht::trySearchInsert's verdict for each candidate ID taken alone against the searches as mirrored: one
      * kad_sr_try_insert_batch_host call. The host then runs insertNode on the searches [lb - back, lb + fwd) only
@@ -901,13 +1025,38 @@ public:
     const kad_searches* handle() const { return ss_; }
 
 private:
-    template <class SearchT>
+    /* When KAD_SN_REMOVABLE is evaluated: never (the overloads without a time), or at a time point. The mirror keeps
+     * the time of every search's upload as nanoseconds since the clock's epoch (INT64_MIN: never). */
+    struct NoTime {
+        template <class NodeT>
+        bool removable(const NodeT&) const { return false; }
+        int64_t ns() const { return INT64_MIN; }
+    };
+    template <class TimePoint>
+    struct At {
+        TimePoint now;
+        template <class NodeT>
+        static bool removableAtPoint(const NodeT& n, TimePoint t) {  // Node::NODE_EXPIRE_TIME = 10 minutes (node.h)
+            return n.isExpired() && n.time + std::chrono::minutes(10) < t;
+        }
+        template <class NodeT>
+        bool removable(const NodeT& n) const { return removableAtPoint(n, now); }
+        template <class NodeT>
+        bool removableAt(const NodeT& n, int64_t ns) const {
+            return removableAtPoint(n, TimePoint(std::chrono::duration_cast<typename TimePoint::duration>(
+                                           std::chrono::nanoseconds(ns))));
+        }
+        int64_t ns() const {
+            return (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(now.time_since_epoch()).count();
+        }
+    };
+    template <class SearchT, class When>
     static void append(const SearchT& s, std::vector<uint8_t>& flags, std::vector<uint32_t>& off,
-                       std::vector<uint8_t>& nid, std::vector<uint8_t>& nfl) {
+                       std::vector<uint8_t>& nid, std::vector<uint8_t>& nfl, const When& when) {
         flags.push_back(s.expired ? (uint8_t)KAD_SR_EXPIRED : (uint8_t)0);
         for (const auto& sn : s.nodes) {
             nid.insert(nid.end(), id_bytes(sn.node->id), id_bytes(sn.node->id) + KAD_HASH_LEN);
-            nfl.push_back(sn.isBad() ? (uint8_t)KAD_SN_BAD : (uint8_t)0);
+            nfl.push_back((uint8_t)((sn.isBad() ? KAD_SN_BAD : 0u) | (when.removable(*sn.node) ? KAD_SN_REMOVABLE : 0u)));
         }
         off.push_back((uint32_t)nfl.size());
     }
@@ -931,6 +1080,7 @@ private:
         ids_.swap(o.ids_);
         std::swap(device_, o.device_);
         std::swap(cap_, o.cap_);
+        at_.swap(o.at_);
     }
 
     kad_searches* ss_ = nullptr;
@@ -938,6 +1088,7 @@ private:
     std::vector<uint8_t> ids_;  // the mirrored search IDs, ascending
     int device_ = 0;
     uint32_t cap_ = 0;
+    std::vector<int64_t> at_;  // per search: when its KAD_SN_REMOVABLE bits were evaluated (INT64_MIN: never set)
 };
 
 /* DhtMirror's search map when the Dht's searches are not mirrored. */
@@ -1009,6 +1160,17 @@ public:
     }
     template <class InfoHashT>
     void syncSearches(sa_family_t af, const std::vector<InfoHashT>& changed) { searches(af).sync(changed); }
+    /* Dht::refill for the searches `ids` of one family from the NodeCache mirror `cache`, at the mirror's clock
+     * (SearchesMirror::refillBatch); syncSearches(af, changed, now) reports the overflowed ones. */
+    template <class NodeMapT, class InfoHashT>
+    std::vector<RefillResult<typename NodeCacheFamilyMirror<NodeMapT>::NodePtr>>
+    refillBatch(const NodeCacheMirror<NodeMapT>& cache, sa_family_t af, const std::vector<InfoHashT>& ids) {
+        return searches(af).refillBatch(cache.family(af), ids, clock_());
+    }
+    template <class InfoHashT>
+    void syncSearches(sa_family_t af, const std::vector<InfoHashT>& changed, time_point now) {
+        searches(af).sync(changed, now);
+    }
     /* Dht::buckets(af) (dht.h:437-438) */
     const RoutingTableMirror<RoutingTableT>& buckets(sa_family_t af) const { return af == AF_INET ? v4_ : v6_; }
     RoutingTableMirror<RoutingTableT>& buckets(sa_family_t af) { return af == AF_INET ? v4_ : v6_; }

@@ -39,6 +39,8 @@ KAD_RESP_FAR, KAD_RESP_FAR4, KAD_RESP_FAR6 = 1, 1, 2
 KAD_NN_NONE, KAD_NN_KNOWN, KAD_NN_REPLACE, KAD_NN_INSERT, KAD_NN_SPLIT, KAD_NN_FULL = 0, 1, 2, 3, 4, 5
 KAD_NN_KIND_MASK, KAD_NN_MYBUCKET, KAD_NN_BOOTSTRAP = 0x0F, 0x10, 1
 KAD_SR_EXPIRED, KAD_SN_BAD = 0x01, 0x01
+KAD_SN_REMOVABLE = 0x02
+KAD_SR_REFILL_OK, KAD_SR_REFILL_OVERFLOW = 0, 1
 KAD_SR_STOP_END, KAD_SR_STOP_KNOWN, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED = 0, 1, 2, 3
 KAD_SWEEP_INCOMING = 1
 
@@ -88,6 +90,7 @@ def shard_block_words(count: int, row_cap: int, part_cap: int) -> int:
 KAD_ERR_INVALID = -1
 KAD_ERR_NOMEM = -3
 KAD_ERR_UNSUPPORTED = -4
+KAD_ERR_NOT_SORTED = -5
 
 ERRORS = {
     -1: "KAD_ERR_INVALID",
@@ -148,6 +151,8 @@ SIGNATURES = {
     "kad_searches_destroy": (C.c_int, [_P]),
     "kad_sr_try_insert_batch": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
     "kad_sr_try_insert_batch_host": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P]),
+    "kad_sr_refill": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "kad_sr_refill_kernel_ms": (C.c_int, [_P, _P]),
     "kad_rt_shard_batch": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
                                      _P, _P]),

@@ -54,6 +54,7 @@
 #include <vector>
 
 #include "../../include/kadgpu.h"
+#include "kad_internal.h"
 #include "kad_mirror_plan.h"
 
 #define KAD_VERSION 100  // 0.1.0
@@ -9269,6 +9270,10 @@ const char* kad_last_error(void) { return g_err.c_str(); }
 namespace kadgpu_internal {
 int set_error(int code, const char* msg) { return set_err(code, "%s", msg); }
 bool device_ok(int dev) { return is_gfx950(dev); }
+// kad_internal.h: the device view of a table's node IDs for kad_searches.hip (kad_sr_refill)
+TableIds table_ids(const kad_table* t) {
+    return TableIds{t->d.key, t->d.tail, t->d.n, t->d.index_base, t->device, (t->flags & KAD_TABLE_SORTED) != 0};
+}
 }  // namespace kadgpu_internal
 
 extern "C" {

@@ -16,20 +16,24 @@
 //                        the threshold, when the search is not full, or when members lie past the trim position.
 // One lane per candidate. A refused candidate costs the lower-bound probes plus the two records beside lb. A walk
 // over a run of accepting searches is serial in its lane (no wave-cooperative path).
+//
+// kad_sr_refill is Dht::refill (dht.cpp:1647-1668) over the same set: the count-14 NodeCache rows
+// of the listed searches, then Search::insertNode on every row node in walk order, applied to the slabs and records
+// in place by refill_kernel, one wave per search with one list entry per lane.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/kadgpu.h"
+#include "kad_internal.h"
 #include "kad_searches_plan.h"
 
-namespace kadgpu_internal {
-int set_error(int code, const char* msg);
-}  // namespace kadgpu_internal
-
+// tests/test_refill_abi.py and tests/test_searches_abi.py hand the argument checks a zeroed buffer for a set: it must
+// read as a set of no searches (S == 0, no pointer followed before the checks end, rf_ms == 0).
 struct kad_searches {
     int device = 0;
     uint32_t S = 0, cap = 0;
@@ -42,6 +46,8 @@ struct kad_searches {
     uint32_t rshift = 0;  // 64 - B
     uint64_t bytes = 0;
     std::vector<uint8_t> h_ids;  // S x 20: a patch checks its lists against the search IDs
+    hipEvent_t rf_ev[2] = {nullptr, nullptr};  // around the last kad_sr_refill's refill kernel
+    float rf_ms = 0.f;
 };
 
 namespace {
@@ -254,6 +260,222 @@ int launch(const kad_searches* ss, const uint8_t* ids, uint32_t q, uint32_t* out
     return KAD_OK;
 }
 
+// ---- kad_sr_refill: Dht::refill over the set ------------------------------------------------------
+// One wave per listed search, one list entry per lane (cap <= 64). An entry lives in its lane's registers as the XOR
+// distance of its ID to the search ID plus its flag byte; Search::insertNode (dht.cpp:961-1047) is then ballots,
+// popcounts and one-lane shifts, and the slab and the record are written once at the end.
+constexpr uint32_t REFILL_MAX_CAP = 64;
+constexpr uint32_t REFILL_WAVES = BLOCK / 64;
+
+struct Ent {
+    uint32_t k0, k1, d2, d3, d4, fl;  // distance words, k1 the most significant; fl the flag byte
+};
+
+__device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+__device__ __forceinline__ uint32_t word_from(uint32_t v, uint32_t src_lane) {
+    return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src_lane << 2), (int)v);
+}
+
+// every lane takes the entry of its lane src (a one-lane shift of the list)
+__device__ __forceinline__ Ent ent_from(const Ent& e, uint32_t src) {
+    return Ent{word_from(e.k0, src), word_from(e.k1, src), word_from(e.d2, src),
+               word_from(e.d3, src), word_from(e.d4, src), word_from(e.fl, src)};
+}
+
+// the entry of one lane, wave-uniform
+__device__ __forceinline__ Ent ent_of_lane(const Ent& e, uint32_t l) {
+    return Ent{(uint32_t)__builtin_amdgcn_readlane((int)e.k0, (int)l), (uint32_t)__builtin_amdgcn_readlane((int)e.k1, (int)l),
+               (uint32_t)__builtin_amdgcn_readlane((int)e.d2, (int)l), (uint32_t)__builtin_amdgcn_readlane((int)e.d3, (int)l),
+               (uint32_t)__builtin_amdgcn_readlane((int)e.d4, (int)l), (uint32_t)__builtin_amdgcn_readlane((int)e.fl, (int)l)};
+}
+
+__device__ __forceinline__ bool ent_same(const Ent& a, const Ent& b) {
+    return a.k0 == b.k0 && a.k1 == b.k1 && a.d2 == b.d2 && a.d3 == b.d3 && a.d4 == b.d4;
+}
+
+// a closer than b: the u64 key first, the tail only on equality
+__device__ __forceinline__ bool ent_closer(const Ent& a, const Ent& b) {
+    const uint64_t ka = ((uint64_t)a.k1 << 32) | a.k0, kb = ((uint64_t)b.k1 << 32) | b.k0;
+    if (ka != kb) return ka < kb;
+    return tail_less(a.d2, a.d3, a.d4, b.d2, b.d3, b.d4);
+}
+
+// The index of the 15th entry that is not BAD, n if there is none: where the trim loop (dht.cpp:1002-1006) and the
+// pop loop (:1031-1035) of a live search both stop. goodm: the ballot of the entries that are not BAD.
+__device__ __forceinline__ uint32_t fifteenth_good(uint64_t goodm, uint32_t lane, uint32_t n) {
+    const bool hit = ((goodm >> lane) & 1ull) && __popcll(goodm & ((1ull << lane) - 1ull)) == (int)KAD_SEARCH_NODES;
+    const uint64_t b = __ballot(hit);
+    return b ? (uint32_t)__builtin_ctzll(b) : n;
+}
+
+// kad_search_trim over the wave (n <= 64)
+__device__ __forceinline__ void wave_trim(bool expired, uint32_t n, uint64_t goodm, uint32_t lane, bool& full,
+                                          uint32_t& t) {
+    if (expired) {
+        full = n >= KAD_SEARCH_NODES;
+        t = full ? KAD_SEARCH_NODES : n;
+    } else {
+        full = (uint32_t)__popcll(goodm) >= KAD_SEARCH_NODES;
+        t = fifteenth_good(goodm, lane, n);
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void refill_targets_kernel(const uint32_t* __restrict__ rec,
+                                                               const uint32_t* __restrict__ which, uint32_t m,
+                                                               uint32_t* __restrict__ targets) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t* r = rec + (uint64_t)SREC_WORDS * which[i];
+    uint32_t* t = targets + 5ull * i;  // the search ID as its 20 bytes
+    t[0] = __builtin_bswap32(r[1]);
+    t[1] = __builtin_bswap32(r[0]);
+    t[2] = __builtin_bswap32(r[2]);
+    t[3] = __builtin_bswap32(r[3]);
+    t[4] = __builtin_bswap32(r[4]);
+}
+
+struct DevRefill {
+    uint32_t* rec;
+    uint64_t* mkey;
+    uint32_t* mtail;
+    uint8_t* mflag;
+    uint32_t cap;
+    const uint64_t* nkey;  // the NodeCache table's node IDs
+    const uint32_t* ntail;
+    uint32_t nn, index_base;
+};
+
+__global__ __launch_bounds__(BLOCK) void refill_kernel(DevRefill D, const uint32_t* __restrict__ which, uint32_t m,
+                                                       const uint32_t* __restrict__ rows,
+                                                       const uint8_t* __restrict__ cnts,
+                                                       uint16_t* __restrict__ out_ins, uint8_t* __restrict__ out_status) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t i = rfl(blockIdx.x * REFILL_WAVES + (threadIdx.x >> 6));
+    if (i >= m) return;
+    const uint32_t s = rfl(which[i]);
+    const uint32_t cnt = D.nn ? min(rfl(cnts[i]), KAD_SEARCH_NODES) : 0u;
+    // the row's node IDs one per lane, the record and the slab: all loads in flight together
+    Ent c = {};
+    if (lane < cnt) {
+        const uint32_t j = min(rows[KAD_SEARCH_NODES * (uint64_t)i + lane] - D.index_base, D.nn - 1u);
+        const uint64_t k = D.nkey[j];
+        const uint32_t* tl = D.ntail + 3ull * j;
+        c = Ent{(uint32_t)k, (uint32_t)(k >> 32), tl[0], tl[1], tl[2], 0u};
+    }
+    uint32_t* r = D.rec + (uint64_t)SREC_WORDS * s;
+    const uint32_t s0 = rfl(r[0]), s1 = rfl(r[1]), s2 = rfl(r[2]), s3 = rfl(r[3]), s4 = rfl(r[4]);
+    uint32_t n = min(rfl(r[SREC_N]), D.cap);
+    bool expired = (rfl(r[SREC_BITS]) & SREC_EXPIRED) != 0;
+    const uint64_t e0 = (uint64_t)s * D.cap + lane;
+    Ent e = {};
+    if (lane < n) {
+        const uint64_t k = D.mkey[e0];
+        const uint32_t* tl = D.mtail + 3ull * e0;
+        e = Ent{(uint32_t)k ^ s0, (uint32_t)(k >> 32) ^ s1, tl[0] ^ s2, tl[1] ^ s3, tl[2] ^ s4, D.mflag[e0]};
+    }
+    c.k0 ^= s0;
+    c.k1 ^= s1;
+    c.d2 ^= s2;
+    c.d3 ^= s3;
+    c.d4 ^= s4;
+
+    uint32_t ins = 0;
+    bool dirty = false, overflow = false;
+    // Lanes at or beyond n hold stale entries by design (a trim or a pop only lowers n): every ballot below masks with
+    // lane < n, a shift up writes lane n before n grows, and the final store writes zeros past n.
+    for (uint32_t j = 0; j < cnt; j++) {  // sr.insertNode(row[j], now), dht.cpp:1659-1663
+        const Ent x = ent_of_lane(c, j);
+        const bool valid = lane < n;  // n <= cap here
+        if (__ballot(valid && ent_same(e, x))) continue;  // found (:972-984)
+        const uint32_t pos = (uint32_t)__popcll(__ballot(valid && ent_closer(e, x)));
+        bool full;
+        uint32_t t;
+        wave_trim(expired, n, __ballot(valid && !(e.fl & KAD_SN_BAD)), lane, full, t);
+        if (full) {  // :1009-1013
+            if (t < n) {
+                n = t;
+                dirty = true;
+            }
+            if (pos >= t) continue;
+        }
+        // insert at pos; a list of cap = 64 entries holds its 65th, wave-uniform, until the pops and the erase
+        Ent sp = {};
+        bool has_sp = false;
+        const Ent up = ent_from(e, (lane - 1u) & 63u);
+        if (n == 64u) {
+            sp = pos == 64u ? x : ent_of_lane(e, 63u);
+            has_sp = true;
+        }
+        if (lane == pos)
+            e = x;
+        else if (lane > pos)
+            e = up;
+        n++;
+        dirty = true;
+        if (expired) {  // a good node revives the search; bad = size - 1, so nothing is popped (:1026-1029)
+            expired = false;
+        } else {  // the pop loop (:1031-1035): back to the 15th entry that is not BAD
+            const uint64_t goodm = __ballot(lane < min(n, 64u) && !(e.fl & KAD_SN_BAD));
+            const uint32_t g = (uint32_t)__popcll(goodm);
+            if (g > KAD_SEARCH_NODES)
+                n = fifteenth_good(goodm, lane, n);
+            else if (has_sp && g == KAD_SEARCH_NODES && !(sp.fl & KAD_SN_BAD))
+                n = 64u;
+            if (n <= 64u) has_sp = false;
+        }
+        // removeExpiredNode (dht.h:628-640): the REMOVABLE entry with the greatest index
+        const uint64_t rm = __ballot(lane < min(n, 64u) && (e.fl & KAD_SN_REMOVABLE));
+        if (has_sp && (sp.fl & KAD_SN_REMOVABLE)) {
+            n = 64u;
+            has_sp = false;
+        } else if (rm) {
+            const uint32_t at = 63u - (uint32_t)__builtin_clzll(rm);
+            Ent dn = ent_from(e, (lane + 1u) & 63u);
+            if (has_sp && lane == 63u) dn = sp;
+            if (lane >= at) e = dn;
+            n--;
+            has_sp = false;
+        }
+        ins |= 1u << j;
+        if (n > D.cap) {
+            overflow = true;
+            break;
+        }
+    }
+
+    if (dirty && !overflow) {  // the slab and the record as kad_searches_create derives them from the new list
+        const bool in = lane < n;
+        if (lane < D.cap) {
+            D.mkey[e0] = in ? ((uint64_t)(e.k1 ^ s1) << 32) | (e.k0 ^ s0) : 0ull;
+            uint32_t* tl = D.mtail + 3ull * e0;
+            tl[0] = in ? e.d2 ^ s2 : 0u;
+            tl[1] = in ? e.d3 ^ s3 : 0u;
+            tl[2] = in ? e.d4 ^ s4 : 0u;
+            D.mflag[e0] = in ? (uint8_t)e.fl : (uint8_t)0;
+        }
+        bool full;
+        uint32_t t;
+        wave_trim(expired, n, __ballot(in && !(e.fl & KAD_SN_BAD)), lane, full, t);
+        if (lane + 1u == t || (t == 0 && lane == 0)) {  // the threshold entry[t-1], zero for t == 0
+            r[SREC_THR] = t ? e.k0 ^ s0 : 0u;
+            r[SREC_THR + 1] = t ? e.k1 ^ s1 : 0u;
+            r[SREC_THR + 2] = t ? e.d2 ^ s2 : 0u;
+            r[SREC_THR + 3] = t ? e.d3 ^ s3 : 0u;
+            r[SREC_THR + 4] = t ? e.d4 ^ s4 : 0u;
+        }
+        if (lane == 0) {
+            r[SREC_N] = n;
+            r[SREC_T] = t;
+            r[SREC_BITS] = (full ? SREC_FULL : 0u) | (expired ? SREC_EXPIRED : 0u);
+        }
+    }
+    if (lane == 0) {
+        out_ins[i] = overflow ? (uint16_t)0 : (uint16_t)ins;
+        out_status[i] = overflow ? (uint8_t)KAD_SR_REFILL_OVERFLOW : (uint8_t)KAD_SR_REFILL_OK;
+    }
+}
+
 void free_device(kad_searches* ss) {
     if (ss->rec) (void)hipFree(ss->rec);
     if (ss->skey) (void)hipFree(ss->skey);
@@ -441,6 +663,8 @@ int kad_searches_destroy(kad_searches* ss) {
     if (ss->S) {
         DeviceGuard g(ss->device);
         (void)hipDeviceSynchronize();
+        for (hipEvent_t e : ss->rf_ev)
+            if (e) (void)hipEventDestroy(e);
         free_device(ss);
     }
     delete ss;
@@ -456,6 +680,78 @@ int kad_sr_try_insert_batch(const kad_searches* ss, const uint8_t* ids, uint32_t
         return set_error(KAD_ERR_INVALID, "device buffers must be 4-byte aligned");
     DeviceGuard g(ss->device);
     return launch(ss, ids, q, out_lb, out_fwd, out_back, out_stop, (hipStream_t)stream);
+}
+
+int kad_sr_refill(kad_searches* ss, const kad_table* nc, uint32_t m, const uint32_t* which, uint32_t* out_rows,
+                  uint8_t* out_cnt, uint16_t* out_inserted, uint8_t* out_status) {
+    if (!ss || !nc) return set_error(KAD_ERR_INVALID, "NULL argument");
+    if (m && (!which || !out_cnt || !out_inserted || !out_status)) return set_error(KAD_ERR_INVALID, "NULL argument");
+    for (uint32_t k = 0; k < m; k++)
+        if (which[k] >= ss->S || (k && which[k] <= which[k - 1]))
+            return set_error(KAD_ERR_INVALID, "patched searches must be strictly ascending and below S");
+    const kadgpu_internal::TableIds T = kadgpu_internal::table_ids(nc);
+    if (!T.sorted) return set_error(KAD_ERR_NOT_SORTED, "NodeCache query needs a KAD_TABLE_SORTED table");
+    if (T.device != ss->device) return set_error(KAD_ERR_INVALID, "search set and NodeCache table on different devices");
+    if (m == 0) return KAD_OK;
+    if (ss->cap > REFILL_MAX_CAP)
+        return set_error(KAD_ERR_UNSUPPORTED, "kad_sr_refill handles slabs of up to 64 entries");
+    DeviceGuard g(ss->device);
+    SR_HIP_TRY(hipDeviceSynchronize());  // queries enqueued before the call read the old set
+    // the call's scratch, one allocation: which, the targets, then the outputs in the order of the one copy back
+    const size_t o_tgt = 4ull * m, o_rows = o_tgt + 20ull * m, o_ins = o_rows + 4ull * KAD_SEARCH_NODES * m,
+                 o_cnt = o_ins + 2ull * m, o_st = o_cnt + m, total = o_st + m;
+    // the host side of the one copy back (rows if asked for, masks, counts, statuses), taken before anything runs: a
+    // failure up to the refill kernel's launch leaves the set unchanged
+    const size_t o_back = out_rows ? o_rows : o_ins;
+    uint8_t* h = new (std::nothrow) uint8_t[total - o_back];
+    if (!h) return set_error(KAD_ERR_NOMEM, "refill: out of host memory");
+    uint8_t* buf = nullptr;
+    if (hipMalloc((void**)&buf, total) != hipSuccess) {
+        (void)hipGetLastError();
+        delete[] h;
+        return set_error(KAD_ERR_NOMEM, "refill: out of device memory");
+    }
+    auto done = [&](int r) {
+        (void)hipFree(buf);
+        delete[] h;
+        return r;
+    };
+    if (!ss->rf_ev[0] && (hipEventCreate(&ss->rf_ev[0]) != hipSuccess || hipEventCreate(&ss->rf_ev[1]) != hipSuccess))
+        return done(set_error(KAD_ERR_HIP, "refill: no events"));
+    if (hipMemcpy(buf, which, 4ull * m, hipMemcpyHostToDevice) != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, "refill: H2D failed"));
+    uint32_t* d_which = (uint32_t*)buf;
+    uint32_t* d_rows = (uint32_t*)(buf + o_rows);
+    hipLaunchKernelGGL(refill_targets_kernel, dim3((m + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, ss->rec, d_which, m,
+                       (uint32_t*)(buf + o_tgt));
+    if (hipGetLastError() != hipSuccess) return done(set_error(KAD_ERR_HIP, "refill: target launch failed"));
+    if (int rc = kad_nc_closest_batch(nc, buf + o_tgt, m, KAD_SEARCH_NODES, d_rows, buf + o_cnt, nullptr)) return done(rc);
+    const DevRefill D{ss->rec, ss->mkey, ss->mtail, ss->mflag, ss->cap, T.key, T.tail, T.n, T.index_base};
+    (void)hipEventRecord(ss->rf_ev[0], nullptr);
+    hipLaunchKernelGGL(refill_kernel, dim3((m + REFILL_WAVES - 1) / REFILL_WAVES), dim3(BLOCK), 0, nullptr, D, d_which, m,
+                       d_rows, buf + o_cnt, (uint16_t*)(buf + o_ins), buf + o_st);
+    const hipError_t le = hipGetLastError();
+    (void)hipEventRecord(ss->rf_ev[1], nullptr);
+    if (le != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, (std::string("refill: launch failed: ") + hipGetErrorString(le)).c_str()));
+    const hipError_t ce = hipMemcpy(h, buf + o_back, total - o_back, hipMemcpyDeviceToHost);
+    if (ce != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, (std::string("refill: D2H failed: ") + hipGetErrorString(ce)).c_str()));
+    if (hipEventElapsedTime(&ss->rf_ms, ss->rf_ev[0], ss->rf_ev[1]) != hipSuccess) {
+        (void)hipGetLastError();
+        ss->rf_ms = 0.f;
+    }
+    if (out_rows) std::memcpy(out_rows, h, o_ins - o_rows);
+    std::memcpy(out_inserted, h + (o_ins - o_back), 2ull * m);
+    std::memcpy(out_cnt, h + (o_cnt - o_back), m);
+    std::memcpy(out_status, h + (o_st - o_back), m);
+    return done(KAD_OK);
+}
+
+int kad_sr_refill_kernel_ms(const kad_searches* ss, float* out_ms) {
+    if (!ss || !out_ms) return set_error(KAD_ERR_INVALID, "NULL argument");
+    *out_ms = ss->rf_ms;
+    return KAD_OK;
 }
 
 int kad_sr_try_insert_batch_host(const kad_searches* ss, const uint8_t* ids, uint32_t q, uint32_t* out_lb,

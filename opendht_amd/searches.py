@@ -12,7 +12,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (KAD_SR_STOP_END, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED, KAD_SR_STOP_KNOWN, check, lib, ptr)
+from ._lib import (KAD_SEARCH_NODES, KAD_SR_REFILL_OVERFLOW, KAD_SR_STOP_END, KAD_SR_STOP_FAR,
+                   KAD_SR_STOP_FAR_EXPIRED, KAD_SR_STOP_KNOWN, check, lib, ptr)
 from .table import _as_ids, _stream_of
 
 STOP_NAMES = {KAD_SR_STOP_END: "end", KAD_SR_STOP_KNOWN: "known", KAD_SR_STOP_FAR: "far",
@@ -137,6 +138,25 @@ class DeviceSearches:
               "kad_sr_try_insert_batch_host")
         return lb, fwd, back, stop
 
+    def refill(self, nc_table, which):
+        """Dht::refill of the searches `which` (strictly ascending indices) from the NodeCache table nc_table, on the
+        device (kad_sr_refill): (rows (m, 14) uint32 padded with KAD_NO_NODE, cnt (m,) uint8, inserted (m,) uint16
+        with bit j = insertNode(row[j]) returned true, status (m,) uint8 KAD_SR_REFILL_*). Synchronous."""
+        which = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
+        m = which.shape[0]
+        rows = np.zeros((m, KAD_SEARCH_NODES), np.uint32)
+        cnt, ins, status = np.zeros(m, np.uint8), np.zeros(m, np.uint16), np.zeros(m, np.uint8)
+        check(lib().kad_sr_refill(self._h, nc_table.handle, m, ptr(which), ptr(rows), ptr(cnt), ptr(ins), ptr(status)),
+              "kad_sr_refill")
+        return rows, cnt, ins, status
+
+    @property
+    def refill_kernel_ms(self) -> float:
+        """The device time of the last refill's refill kernel (kad_sr_refill_kernel_ms)."""
+        ms = C.c_float()
+        check(lib().kad_sr_refill_kernel_ms(self._h, C.byref(ms)), "kad_sr_refill_kernel_ms")
+        return ms.value
+
 
 def apply_search_verdicts(host, S: int, lb, fwd, back, stop, trims):
     """The host half of try_search_insert: the candidates in order against the verdicts (host arrays) of one
@@ -226,5 +246,58 @@ def try_search_insert(DS: DeviceSearches, host, cand_ids) -> dict:
         if longest <= DS.cap:
             DS.patch(which, flags, off, nid, nfl)
         else:  # a list outgrew the slabs (bad nodes do not count towards SEARCH_NODES): a new set
+            DS.recreate(*states(range(DS.S)), cap=max(longest, 2 * DS.cap))
+    return counts
+
+
+def refill_searches(DS: DeviceSearches, NC, host, which, now) -> dict:
+    """Dht::refill (dht.cpp:1647-1668) for the searches `which` (strictly ascending indices) of DS from the NodeCache
+    table NC, with one device refill. `host` holds the real searches: host.insert_row(s, row) runs
+    sr.insertNode(node, now) on search s for every node index of the row in order and returns the mask of the
+    inserts that returned true; host.state(s, now) -> (flags, node_ids, node_flags) is its state afterwards, with
+    KAD_SN_REMOVABLE evaluated at `now`. The device has already applied the same walk to its own copy, so the host
+    replays the whole row (a refused insert can still trim) and nothing is uploaded, except for the searches the
+    device reports as KAD_SR_REFILL_OVERFLOW: those it left untouched, and they are patched from the host's lists,
+    or the set is created again with larger slabs when a list no longer fits (as try_search_insert does).
+
+    Returns {"refilled", "overflowed", "inserts", "untouched"}: searches the device refilled, searches it left to the
+    host, inserts that returned true, searches whose row was empty."""
+    which = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
+    counts = {"refilled": 0, "overflowed": 0, "inserts": 0, "untouched": 0}
+    if which.shape[0] == 0:
+        return counts
+    rows, cnt, ins, status = DS.refill(NC, which)
+    over = []
+    for k, s in enumerate(which):
+        if cnt[k] == 0:  # dht.cpp:1652-1656
+            counts["untouched"] += 1
+            continue
+        mask = int(host.insert_row(int(s), rows[k, :cnt[k]]))
+        counts["inserts"] += bin(mask).count("1")
+        if status[k] == KAD_SR_REFILL_OVERFLOW:
+            over.append(int(s))
+            counts["overflowed"] += 1
+        else:
+            if mask != int(ins[k]):
+                raise RuntimeError(f"refill_searches: search {int(s)} inserted {mask:#x}, the device {int(ins[k]):#x}")
+            counts["refilled"] += 1
+
+    def states(idx):
+        flags, off, nid, nfl = [], [0], [np.zeros((0, 20), np.uint8)], [np.zeros(0, np.uint8)]
+        for s in idx:
+            fl, ids_s, nf_s = host.state(int(s), now)
+            flags.append(fl)
+            if len(ids_s):
+                nid.append(_as_ids(ids_s))
+                nfl.append(np.asarray(nf_s, dtype=np.uint8).reshape(-1))
+            off.append(off[-1] + len(ids_s))
+        return np.array(flags, np.uint8), np.array(off, np.uint32), np.concatenate(nid), np.concatenate(nfl)
+
+    if over:
+        flags, off, nid, nfl = states(over)
+        longest = int(np.diff(off).max())
+        if longest <= DS.cap:
+            DS.patch(np.array(over, np.uint32), flags, off, nid, nfl)
+        else:
             DS.recreate(*states(range(DS.S)), cap=max(longest, 2 * DS.cap))
     return counts
