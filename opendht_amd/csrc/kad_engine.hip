@@ -9045,6 +9045,8 @@ int build_ncl(kad_table* t) {
     uint64_t fb = 0;
     int rc;
     if ((rc = dev_upload(&lp, nullptr, (size_t)(NCL_STRIDE + NCL2_DWORDS) * d.nslots, fresh, fb))) return rc;
+    // a deferred line is its header alone: the bytes after it are zero, so that equal tables hold equal arrays
+    (void)hipMemsetAsync(lp, 0, 4ull * (NCL_STRIDE + NCL2_DWORDS) * d.nslots, build_stream(t));
     hipLaunchKernelGGL(ncl_build_kernel, dim3(grid_for(d.nslots)), dim3(BLOCK), 0, build_stream(t), d.key, d.status, d.nrdx, d.nslots,
                        d.n, 64 - d.nshift, lp, LineSel{});
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(build_stream(t)) != hipSuccess) {
@@ -9064,6 +9066,7 @@ int build_ncl32(kad_table* t) {
     uint64_t fb = 0;
     int rc;
     if ((rc = dev_upload(&lp, nullptr, (size_t)NC32_STRIDE * d.nslots, fresh, fb))) return rc;
+    (void)hipMemsetAsync(lp, 0, 4ull * NC32_STRIDE * d.nslots, build_stream(t));  // as build_ncl
     hipLaunchKernelGGL(ncl32_build_kernel, dim3(grid_for(8ull * d.nslots)), dim3(BLOCK), 0, build_stream(t), d.key, d.status, d.nrdx,
                        d.nslots, d.n, 64 - d.nshift, lp, LineSel{});
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(build_stream(t)) != hipSuccess) {
@@ -11328,6 +11331,9 @@ int kad_nc_apply(kad_table* t, const uint32_t* erase, uint32_t n_erase, const ui
     if (n1) {
         hipLaunchKernelGGL(nc_radix_kernel, dim3(grid_for((uint64_t)r.slots + 1)), dim3(BLOCK), 0, 0, key1, n1, r.base,
                            r.shift, r.slots, rdx1);
+        // as build_ncl: the bytes after a deferred line's header are zero
+        if (has_ncl) (void)hipMemsetAsync(ncl1, 0, 4ull * (NCL_STRIDE + NCL2_DWORDS) * r.slots, 0);
+        if (has_ncl32) (void)hipMemsetAsync(ncl32, 0, 4ull * NC32_STRIDE * r.slots, 0);
         if (has_ncl)
             hipLaunchKernelGGL(ncl_build_kernel, dim3(grid_for(r.slots)), dim3(BLOCK), 0, 0, key1, st1, rdx1, r.slots, n1,
                                64 - r.shift, ncl1, LineSel{});

@@ -205,7 +205,9 @@ int mirror_plan(const std::vector<uint32_t>& off0, const uint8_t* first0, uint32
                                     : o + 1 < B0                                  ? first0 + 20ull * (o + 1)
                                                                                   : nullptr;
                 const uint8_t* id = new_ids + 20ull * b;
-                if (std::memcmp(lo, id, 20) > 0 || (hi && std::memcmp(id, hi, 20) >= 0))
+                // an ID below the table's first bucket belongs to that bucket (findBucket clamps, as KAD_OP_INSERT below)
+                const bool below_ok = o == 0 && sub == 0;
+                if ((!below_ok && std::memcmp(lo, id, 20) > 0) || (hi && std::memcmp(id, hi, 20) >= 0))
                     return fail(err, "op %u: new node %u does not belong to node %u's bucket", k, b, a);
             }
             PB& p = touch(o)[sub];

@@ -9,8 +9,9 @@ import torch
 
 import oracle as O
 import tables as TB
+from mutation_model import random_ops as _random_ops
 from opendht_amd import DeviceTable
-from opendht_amd._lib import KAD_OP_INSERT, KAD_OP_REMOVE, KAD_OP_REPLACE, KAD_OP_SPLIT
+from opendht_amd._lib import KAD_OP_SPLIT
 
 
 def test_oracle_split_known_answer():
@@ -23,46 +24,6 @@ def test_oracle_split_known_answer():
     assert first[1, 0] == 0x80 and list(off) == [0, 2, 3]
     assert [r[0] for r in out_ids] == [0x20, 0x10, 0x90] and list(remap) == [1, 2, 0]
     F.close()
-
-
-def _random_ops(t, rng, n_ops, allow_split=True):
-    """A random batch: removals, in-bucket replacements, insertions, splits (old nodes used once)."""
-    n = t["ids"].shape[0]
-    B = t["first"].shape[0]
-    order = rng.permutation(n)
-    used = 0
-    ops, new_ids, new_st = [], [], []
-    existing = {bytes(x) for x in t["ids"]}
-    cur_B = B
-    for _ in range(n_ops):
-        r = rng.random()
-        if r < 0.3 and used < n:
-            ops.append((KAD_OP_REMOVE, int(order[used]), 0))
-            used += 1
-        elif r < 0.55 and used < n:
-            a = int(order[used])
-            used += 1
-            nid = t["ids"][a].copy()
-            nid[12:] = rng.integers(0, 256, 8, dtype=np.uint8)  # same bucket (depth <= 96)
-            if bytes(nid) in existing:
-                continue
-            existing.add(bytes(nid))
-            ops.append((KAD_OP_REPLACE, a, len(new_ids)))
-            new_ids.append(nid)
-            new_st.append(rng.integers(0, 3))
-        elif r < 0.9 or not allow_split:
-            nid = rng.integers(0, 256, 20, dtype=np.uint8)
-            if bytes(nid) in existing:
-                continue
-            existing.add(bytes(nid))
-            ops.append((KAD_OP_INSERT, len(new_ids), 0))
-            new_ids.append(nid)
-            new_st.append(rng.integers(0, 3))
-        else:
-            ops.append((KAD_OP_SPLIT, int(rng.integers(0, cur_B)), 0))
-            cur_B += 1
-    new_ids = np.array(new_ids, np.uint8).reshape(-1, 20)
-    return np.array(ops, np.uint32).reshape(-1, 3), new_ids, np.array(new_st, np.uint8)
 
 
 def _mirror_tables():
