@@ -258,6 +258,10 @@ def test_owner_route_keys_ties(gpu, ti):
         tailed = R.tailed(combine=False)
         if ti != 4:
             assert tailed, "a top-64 tie (or a table without short lines) must ask for the full targets"
+        else:
+            top = np.ascontiguousarray(t["ids"][:, :8]).view(">u8").reshape(-1)
+            assert np.unique(top).size == top.size  # no two nodes share their top 64 bits: the keys order every window
+            assert not tailed, "the keys answer every query of a table without top-64 ties"
         oi, oc, R = serve_owner(T, d, 8, route=R)
         torch.cuda.synchronize()
         want, wcnt = O.flat_rt_closest(t["ids"], t["status"], t["first"], t["off"], tg, 8, nthreads=8)
