@@ -492,12 +492,41 @@ int kad_searches_create(kad_searches** out, int device, uint32_t S, uint32_t cap
                         const uint8_t* flags, const uint32_t* off, const uint8_t* node_ids, const uint8_t* node_flags);
 /* Replaces the flags and lists of the m searches which[0..m) (strictly ascending, < S: KAD_ERR_INVALID otherwise):
  * the ones the host's inserts changed. flags m bytes, off[m + 1], node arrays as for create, the same checks in the
- * same order. The set of search IDs is fixed: adding or erasing a search is a new set. Synchronous, and as
+ * same order. The set of search IDs is not changed here: kad_searches_apply adds and erases searches. Synchronous, and as
  * kad_table_apply towards queries: it first waits for all device work enqueued before the call, so a query enqueued
  * earlier reads the old set and one enqueued after the return the new one; the caller must not enqueue queries on
  * the set from another thread while the call runs. Failure leaves the set unchanged. m == 0: KAD_OK. */
 int kad_searches_patch(kad_searches* ss, uint32_t m, const uint32_t* which, const uint8_t* flags, const uint32_t* off,
                        const uint8_t* node_ids, const uint8_t* node_flags);
+/* Adds and erases searches and grows the slabs on the device (Dht::search dht.cpp:1673-1735, the re-use of a done
+ * search under a new ID :1695-1711, Dht::expireSearches :1060-1074). Host arrays, synchronous.
+ *   erase     n_erase indices as of the call, strictly ascending, < S: these searches go.
+ *   insert    n_ins new searches, ins_ids n_ins x 20 bytes in any order, distinct and different from every kept
+ *             search's ID (the ID of a search erased by the same call is allowed: the re-use case). A new search is
+ *             empty: n = 0, t = 0, full = 0, threshold zero, slab all zero, KAD_SR_EXPIRED from ins_flags[j] (NULL
+ *             ins_flags: all 0): exactly the record and slab kad_searches_create derives for an empty list.
+ *   kept      record, member keys, tails and flag bytes are carried over bit for bit (KAD_SN_BAD, KAD_SN_REMOVABLE and
+ *             any other bit the caller stored); only the position changes. The new set is in ascending ID order.
+ *   new_cap   0 keeps cap; otherwise >= cap, and every slab becomes new_cap entries with entries [cap, new_cap) zero.
+ *             Slabs do not shrink. new_cap alone is "create the set again with larger slabs" without the upload.
+ *   lookup    skey (S' <= 4096) or the prefix directory (B = ceil(log2 S') at most 24) is rebuilt on the device for
+ *             the new S'; kad_searches_info's device_bytes equals what kad_searches_create of the final set reports.
+ *   outputs   remap (S words, may be NULL): the new index of every old search, KAD_NO_NODE if erased; new_index
+ *             (n_ins words, may be NULL): the index of every inserted search. Written on success only.
+ * Only one word per new search and the 20 bytes of every inserted ID go up; records and slabs never do.
+ * Failure-atomic as kad_table_apply and kad_nc_apply: the new arrays are allocated and filled beside the old ones and
+ * take their place only after the last device step succeeded, so every failure leaves the set unchanged and the peak
+ * device memory of the call is the old set plus the new one. The refill timing of kad_sr_refill_kernel_ms survives.
+ * As kad_searches_patch towards queries: it first waits for all device work enqueued before the call, so a query
+ * enqueued earlier reads the old set and one enqueued after the return the new one.
+ * Checked in this order, before any device work: NULL ss; NULL erase with n_erase > 0 or NULL ins_ids with n_ins > 0;
+ * erase not strictly ascending or not < S; new_cap != 0 && new_cap < cap; an ins_flags byte with bits other than
+ * KAD_SR_EXPIRED; inserted IDs not distinct or one equal to a kept search's ID; S' x cap' >= 0x7FFFFFFF (all
+ * KAD_ERR_INVALID); nothing to do (n_erase = n_ins = 0 and new_cap 0 or cap): KAD_OK, remap = identity, no device work.
+ * Out of host or device memory: KAD_ERR_NOMEM. S' == 0 leaves a set without device arrays, as kad_searches_create with
+ * S == 0; such a set accepts inserts. */
+int kad_searches_apply(kad_searches* ss, const uint32_t* erase, uint32_t n_erase, const uint8_t* ins_ids,
+                       const uint8_t* ins_flags, uint32_t n_ins, uint32_t new_cap, uint32_t* remap, uint32_t* new_index);
 /* S, cap and the device bytes held (any may be NULL). */
 int kad_searches_info(const kad_searches* ss, uint32_t* S, uint32_t* cap, uint64_t* device_bytes);
 /* The device state read back into host arrays (any may be NULL): ids S x 20, flags S, n S words, node_ids
@@ -542,7 +571,7 @@ int kad_sr_try_insert_batch_host(const kad_searches* ss, const uint8_t* ids, uin
  * reported by the host (kad_table_patch_times).
  * A list may not outgrow its slab: a search whose list would hold more than cap entries after some insertNode of its
  * row returns gets KAD_SR_REFILL_OVERFLOW, is left byte for byte as it was, and its inserted mask is 0 (row and cnt
- * are still written); the host runs the walk from the row and creates the set again with a larger cap.
+ * are still written); the host runs the walk from the row and grows the slabs (kad_searches_apply with new_cap).
  * Host arrays, synchronous; as kad_searches_patch towards queries (it first waits for all device work enqueued before
  * the call). which: m search indices, strictly ascending, < S. out_rows: m x KAD_SEARCH_NODES, padded with KAD_NO_NODE,
  * may be NULL; out_cnt m bytes; out_inserted m words of 16 bits, bit j = insertNode(row[j]) returned true; out_status m

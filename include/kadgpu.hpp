@@ -881,13 +881,29 @@ private:
 
 public:
     /* The searches with these IDs changed their list or flags (the host's inserts, a node turning bad, expiry):
-     * one kad_searches_patch. A search added to or erased from the map needs a new snapshot (KAD_ERR_INVALID for an
-     * ID that is not mirrored); a list that outgrew the slabs takes one by itself. */
+     * one kad_searches_patch. A search added to or erased from the map is reported to update() (KAD_ERR_INVALID
+     * here for an ID that is not mirrored); a list that outgrew the slabs takes a new snapshot by itself. */
     template <class InfoHashT>
     void sync(const std::vector<InfoHashT>& changed) { syncAt(changed, NoTime()); }
     /* The same with KAD_SN_REMOVABLE evaluated at `now` (see snapshot). */
     template <class InfoHashT, class TimePoint, class = typename TimePoint::duration>
     void sync(const std::vector<InfoHashT>& changed, TimePoint now) { syncAt(changed, At<TimePoint>{now}); }
+
+    /* The host's map lost the searches `erased` (Dht::expireSearches dht.cpp:1060-1074, or a done search re-used under
+     * a new ID :1695-1711) and gained `added` (Dht::search :1691-1693), both already applied to the map: one
+     * kad_searches_apply, which moves the kept searches on the device and uploads nothing but the new IDs. The new
+     * searches enter empty; those of `added` whose host list already holds nodes then take one sync. An ID in `erased`
+     * that is not mirrored, an ID in `added` that is mirrored and not in `erased`, or one that is not in the map:
+     * KAD_ERR_INVALID, and the mirror is unchanged. Dht::search goes on with refillBatch on the new IDs (:1728). */
+    template <class InfoHashT>
+    void update(const std::vector<InfoHashT>& erased, const std::vector<InfoHashT>& added) {
+        updateAt(erased, added, NoTime());
+    }
+    /* The same with KAD_SN_REMOVABLE evaluated at `now` for the lists that are synced (see snapshot). */
+    template <class InfoHashT, class TimePoint, class = typename TimePoint::duration>
+    void update(const std::vector<InfoHashT>& erased, const std::vector<InfoHashT>& added, TimePoint now) {
+        updateAt(erased, added, At<TimePoint>{now});
+    }
 
     /* Dht::refill (dht.cpp:1647-1668) of the searches `ids` (distinct, mirrored) from the NodeCache family mirror
      * `nc` on the device: one kad_sr_refill. Searches whose KAD_SN_REMOVABLE bits at `now` differ from the mirrored
@@ -1001,6 +1017,44 @@ private:
         for (uint32_t w : which) at_[w] = when.ns();
     }
 
+    template <class InfoHashT, class When>
+    void updateAt(const std::vector<InfoHashT>& erased, const std::vector<InfoHashT>& added, const When& when) {
+        if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::update before snapshot");
+        std::vector<uint32_t> erase;
+        for (const auto& id : erased) erase.push_back(index_of(id_bytes(id)));
+        std::sort(erase.begin(), erase.end());
+        erase.erase(std::unique(erase.begin(), erase.end()), erase.end());
+        std::vector<uint8_t> ins, fl;
+        std::vector<InfoHashT> filled;  // added searches that already hold nodes
+        for (const auto& id : added) {
+            const uint32_t at = lower_bound_of(id_bytes(id));
+            if (at < size() && std::memcmp(&ids_[(size_t)at * KAD_HASH_LEN], id_bytes(id), KAD_HASH_LEN) == 0 &&
+                !std::binary_search(erase.begin(), erase.end(), at))
+                throw Error(KAD_ERR_INVALID, "SearchesMirror::update: an added search is already mirrored");
+            const auto it = map_->find(id);
+            if (it == map_->end()) throw Error(KAD_ERR_INVALID, "SearchesMirror::update: an added search is not in the map");
+            ins.insert(ins.end(), id_bytes(id), id_bytes(id) + KAD_HASH_LEN);
+            fl.push_back(it->second->expired ? (uint8_t)KAD_SR_EXPIRED : (uint8_t)0);
+            if (!it->second->nodes.empty()) filled.push_back(id);
+        }
+        std::vector<uint32_t> remap(size()), new_index(added.size());
+        check(kad_searches_apply(ss_, erase.data(), (uint32_t)erase.size(), ins.data(), fl.data(), (uint32_t)added.size(),
+                                 0, remap.data(), new_index.data()), "kad_searches_apply");
+        const size_t S2 = size() - erase.size() + added.size();
+        std::vector<uint8_t> ids(S2 * KAD_HASH_LEN);
+        std::vector<int64_t> at(S2, when.ns());
+        for (size_t s = 0; s < remap.size(); s++)
+            if (remap[s] != KAD_NO_NODE) {
+                std::memcpy(&ids[(size_t)remap[s] * KAD_HASH_LEN], &ids_[s * KAD_HASH_LEN], KAD_HASH_LEN);
+                at[remap[s]] = at_[s];
+            }
+        for (size_t j = 0; j < new_index.size(); j++)
+            std::memcpy(&ids[(size_t)new_index[j] * KAD_HASH_LEN], &ins[j * KAD_HASH_LEN], KAD_HASH_LEN);
+        ids_.swap(ids);
+        at_.swap(at);
+        if (!filled.empty()) syncAt(filled, when);
+    }
+
 public:
 
     /* Dht::trySearchInsert's verdict for each candidate ID taken alone against the searches as mirrored: one
@@ -1060,12 +1114,16 @@ private:
         }
         off.push_back((uint32_t)nfl.size());
     }
-    uint32_t index_of(const uint8_t* id) const {
+    uint32_t lower_bound_of(const uint8_t* id) const {
         size_t lo = 0, hi = size();
         while (lo < hi) {
             const size_t mid = (lo + hi) / 2;
             if (std::memcmp(&ids_[mid * KAD_HASH_LEN], id, KAD_HASH_LEN) < 0) lo = mid + 1; else hi = mid;
         }
+        return (uint32_t)lo;
+    }
+    uint32_t index_of(const uint8_t* id) const {
+        const size_t lo = lower_bound_of(id);
         if (lo == size() || std::memcmp(&ids_[lo * KAD_HASH_LEN], id, KAD_HASH_LEN) != 0)
             throw Error(KAD_ERR_INVALID, "search not in the mirrored snapshot (snapshot again)");
         return (uint32_t)lo;
@@ -1170,6 +1228,12 @@ public:
     template <class InfoHashT>
     void syncSearches(sa_family_t af, const std::vector<InfoHashT>& changed, time_point now) {
         searches(af).sync(changed, now);
+    }
+    /* The searches of one family erased from and added to the Dht's map (SearchesMirror::update), at the mirror's
+     * clock: Dht::expireSearches and Dht::search. */
+    template <class InfoHashT>
+    void updateSearches(sa_family_t af, const std::vector<InfoHashT>& erased, const std::vector<InfoHashT>& added) {
+        searches(af).update(erased, added, clock_());
     }
     /* Dht::buckets(af) (dht.h:437-438) */
     const RoutingTableMirror<RoutingTableT>& buckets(sa_family_t af) const { return af == AF_INET ? v4_ : v6_; }

@@ -16,7 +16,7 @@ from ._lib import (KAD_SN_BAD, KAD_SR_EXPIRED, KAD_SR_STOP_END, KAD_SR_STOP_FAR,
 from ._lib import KAD_SN_REMOVABLE, KAD_SR_REFILL_OK, KAD_SR_REFILL_OVERFLOW
 from ._lib import KAD_SWEEP_INCOMING
 from .ingest import ingest
-from .searches import DeviceSearches, refill_searches, try_search_insert
+from .searches import DeviceSearches, expire_searches, refill_searches, start_searches, try_search_insert
 from .table import DeviceTable, nc_closest_dual, rt_closest_dual, rt_responsible_dual
 
 __all__ = [
@@ -28,4 +28,5 @@ __all__ = [
     "KAD_SN_BAD", "KAD_SR_EXPIRED", "KAD_SR_STOP_END", "KAD_SR_STOP_FAR", "KAD_SR_STOP_FAR_EXPIRED",
     "KAD_SR_STOP_KNOWN", "DeviceSearches", "try_search_insert", "KAD_SWEEP_INCOMING",
     "KAD_SN_REMOVABLE", "KAD_SR_REFILL_OK", "KAD_SR_REFILL_OVERFLOW", "refill_searches",
+    "start_searches", "expire_searches",
 ]

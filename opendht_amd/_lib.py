@@ -146,6 +146,7 @@ SIGNATURES = {
     "kad_search_trim": (C.c_int, [C.c_uint32, _P, C.c_uint32, _P, _P]),
     "kad_searches_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]),
     "kad_searches_patch": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "kad_searches_apply": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P, _P]),
     "kad_searches_info": (C.c_int, [_P, _P, _P, _P]),
     "kad_searches_export": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "kad_searches_destroy": (C.c_int, [_P]),

@@ -20,11 +20,17 @@
 // kad_sr_refill is Dht::refill (dht.cpp:1647-1668) over the same set: the count-14 NodeCache rows
 // of the listed searches, then Search::insertNode on every row node in walk order, applied to the slabs and records
 // in place by refill_kernel, one wave per search with one list entry per lane.
+//
+// kad_searches_apply changes the membership (Dht::search dht.cpp:1673-1735, Dht::expireSearches
+// :1060-1074) and the slab size: the host plans one source word per new search, searches_relayout_kernel gathers the
+// records and slabs into new arrays beside the old ones, searches_rdx_kernel rebuilds the prefix directory, and the
+// handle's arrays are swapped once everything succeeded.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
 #include <new>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -32,8 +38,9 @@
 #include "kad_internal.h"
 #include "kad_searches_plan.h"
 
-// tests/test_refill_abi.py and tests/test_searches_abi.py hand the argument checks a zeroed buffer for a set: it must
-// read as a set of no searches (S == 0, no pointer followed before the checks end, rf_ms == 0).
+// tests/test_refill_abi.py, test_searches_abi.py and test_searches_apply_abi.py hand the argument checks a zeroed
+// buffer for a set: it must read as a set of no searches (S == 0, cap == 0, no pointer followed before the checks end,
+// rf_ms == 0).
 struct kad_searches {
     int device = 0;
     uint32_t S = 0, cap = 0;
@@ -476,6 +483,167 @@ __global__ __launch_bounds__(BLOCK) void refill_kernel(DevRefill D, const uint32
     }
 }
 
+// ---- kad_searches_apply: add and erase searches, grow the slabs -----------------------------------
+// The new set is written beside the old one: every record and slab is gathered from src[s'] (kadplan::SRC_NEW: an
+// inserted search, zero-filled, its record from the 20 uploaded ID bytes). A streaming gather, read once with
+// non-temporal loads and written once; one thread per unit of the four arrays taken one after the other, so
+// neighbouring lanes write neighbouring units. WIDE (old and new cap multiples of 16: every slab starts on a 16-byte
+// boundary) moves 16-byte units throughout. Otherwise a key is one 8-byte unit, a tail three words, and the flag bytes,
+// whose per-search slabs then start at any byte, are assembled into the words of the new array taken as a whole.
+constexpr uint32_t SRC_EXPIRED = 0x40000000u;  // with SRC_NEW: the inserted search is KAD_SR_EXPIRED
+constexpr uint32_t SRC_SLOT = SRC_EXPIRED - 1u;
+constexpr uint32_t RELAYOUT_GRID = 4096;  // grid-stride beyond
+
+struct DevRelayout {
+    const u32x4_t* rec;  // the old set
+    const uint64_t* mkey;
+    const uint32_t* mtail;
+    const uint8_t* mflag;
+    u32x4_t* nrec;  // the new one
+    uint64_t* nskey;  // NULL for a set with a prefix directory
+    uint64_t* nmkey;
+    uint32_t* nmtail;
+    uint8_t* nmflag;
+    const uint32_t* src;
+    const uint32_t* ins_ids;  // n_ins x 5 words, the inserted IDs as their bytes
+    uint32_t S2, cap, cap2;
+};
+
+// unit j (16 bytes) of the record kad_searches_create derives for an empty search
+__device__ __forceinline__ u32x4_t empty_rec_unit(const uint32_t* id, uint32_t j, bool expired) {
+    u32x4_t v = {0u, 0u, 0u, 0u};
+    if (j == 0) {
+        v.x = __builtin_bswap32(id[1]);
+        v.y = __builtin_bswap32(id[0]);
+        v.z = __builtin_bswap32(id[2]);
+        v.w = __builtin_bswap32(id[3]);
+    } else if (j == 1) {
+        v.x = __builtin_bswap32(id[4]);
+    } else if (j == 3) {
+        v.x = expired ? SREC_EXPIRED : 0u;
+    }
+    return v;
+}
+
+// unit j of per_new of the slab of new search s: the old search's unit, zero past its per_old units or for a new one
+template <class T>
+__device__ __forceinline__ T gather_unit(const T* old, uint32_t w, uint32_t j, uint32_t per_old) {
+    T v = {};
+    if (!(w & kadplan::SRC_NEW) && j < per_old) v = __builtin_nontemporal_load(old + (uint64_t)w * per_old + j);
+    return v;
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(BLOCK) void searches_relayout_kernel(DevRelayout D) {
+    const uint32_t cap = D.cap, cap2 = D.cap2;
+    const uint32_t kn = WIDE ? cap2 / 2 : cap2, ko = WIDE ? cap / 2 : cap;             // key units per search
+    const uint32_t tn = WIDE ? cap2 / 4 * 3 : cap2, to = WIDE ? cap / 4 * 3 : cap;     // tail units
+    const uint64_t fbytes = (uint64_t)D.S2 * cap2;
+    const uint64_t n_rec = 4ull * D.S2, n_key = (uint64_t)D.S2 * kn, n_tail = (uint64_t)D.S2 * tn,
+                   n_flag = WIDE ? fbytes / 16 : (fbytes + 3) / 4;
+    const uint64_t total = n_rec + n_key + n_tail + n_flag;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (uint64_t)gridDim.x * BLOCK) {
+        if (i < n_rec) {
+            const uint32_t s = (uint32_t)(i >> 2), j = (uint32_t)i & 3u, w = D.src[s];
+            u32x4_t v;
+            if (w & kadplan::SRC_NEW)
+                v = empty_rec_unit(D.ins_ids + 5ull * (w & SRC_SLOT), j, (w & SRC_EXPIRED) != 0);
+            else
+                v = __builtin_nontemporal_load(D.rec + 4ull * w + j);
+            D.nrec[i] = v;
+            if (j == 0 && D.nskey) D.nskey[s] = ((uint64_t)v.y << 32) | v.x;
+        } else if (i - n_rec < n_key) {
+            const uint32_t l = (uint32_t)(i - n_rec), s = l / kn, j = l - s * kn, w = D.src[s];
+            if (WIDE)
+                reinterpret_cast<u32x4_t*>(D.nmkey)[l] = gather_unit(reinterpret_cast<const u32x4_t*>(D.mkey), w, j, ko);
+            else
+                D.nmkey[l] = gather_unit(D.mkey, w, j, ko);
+        } else if (i - n_rec - n_key < n_tail) {
+            const uint32_t l = (uint32_t)(i - n_rec - n_key), s = l / tn, j = l - s * tn, w = D.src[s];
+            if (WIDE) {
+                reinterpret_cast<u32x4_t*>(D.nmtail)[l] =
+                    gather_unit(reinterpret_cast<const u32x4_t*>(D.mtail), w, j, to);
+            } else {
+                const bool in = !(w & kadplan::SRC_NEW) && j < to;
+                const uint32_t* o = D.mtail + 3ull * ((uint64_t)(in ? w : 0u) * cap + (in ? j : 0u));
+                uint32_t t0 = 0, t1 = 0, t2 = 0;
+                if (in) {
+                    t0 = __builtin_nontemporal_load(o);
+                    t1 = __builtin_nontemporal_load(o + 1);
+                    t2 = __builtin_nontemporal_load(o + 2);
+                }
+                uint32_t* d = D.nmtail + 3ull * l;
+                d[0] = t0;
+                d[1] = t1;
+                d[2] = t2;
+            }
+        } else {
+            const uint32_t l = (uint32_t)(i - n_rec - n_key - n_tail);
+            if (WIDE) {
+                const uint32_t fn = cap2 / 16, s = l / fn, j = l - s * fn;
+                reinterpret_cast<u32x4_t*>(D.nmflag)[l] =
+                    gather_unit(reinterpret_cast<const u32x4_t*>(D.mflag), D.src[s], j, cap / 16);
+            } else {  // word l of the new flag array: bytes 4l .. 4l+3, each of its own search and entry
+                const uint32_t b0 = 4u * l;  // below S' x cap' < 2^31
+                uint32_t s = b0 / cap2, j = b0 - s * cap2, word = 0;
+                const uint32_t nb = fbytes - b0 < 4 ? (uint32_t)(fbytes - b0) : 4u;
+                for (uint32_t k = 0; k < nb; k++) {
+                    const uint32_t w = D.src[s];
+                    if (!(w & kadplan::SRC_NEW) && j < cap)
+                        word |= (uint32_t)__builtin_nontemporal_load(D.mflag + (uint64_t)w * cap + j) << (8 * k);
+                    if (++j == cap2) {
+                        j = 0;
+                        s++;
+                    }
+                }
+                if (nb == 4)
+                    reinterpret_cast<uint32_t*>(D.nmflag)[l] = word;
+                else  // the array's last bytes
+                    for (uint32_t k = 0; k < nb; k++) D.nmflag[b0 + k] = (uint8_t)(word >> (8 * k));
+            }
+        }
+    }
+}
+
+// The prefix directory of a large set from the new records: rdx[p] = the number of search keys whose top B bits are
+// below p, p = 0 .. 2^B, by a lower bound over the ascending keys.
+__global__ __launch_bounds__(BLOCK) void searches_rdx_kernel(const u32x4_t* __restrict__ rec, uint32_t S, uint32_t rshift,
+                                                             uint32_t slots, uint32_t* __restrict__ rdx) {
+    const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= slots) return;
+    uint32_t lo = 0, hi = S;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        const u32x4_t r0 = rec[4ull * mid];
+        const uint64_t k = ((uint64_t)r0.y << 32) | r0.x;
+        if ((uint32_t)(k >> rshift) < p)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    rdx[p] = lo;
+}
+
+// The arrays of a set of S searches with slabs of cap entries: their sizes and the directory's B (0: dense skey).
+struct Layout {
+    size_t b_rec, b_skey, b_mkey, b_mtail, b_mflag, b_rdx;
+    uint32_t B;
+    Layout(uint32_t S, uint32_t cap) {
+        B = 0;
+        if (S > LDS_KEYS) {
+            B = 1;
+            while (B < 24 && (1u << B) < S) B++;
+        }
+        b_rec = 64ull * S;
+        b_skey = B ? 0 : 8ull * S;
+        b_mkey = 8ull * S * cap;
+        b_mtail = 12ull * S * cap;
+        b_mflag = (size_t)S * cap;
+        b_rdx = B ? 4ull * ((1ull << B) + 1) : 0;
+    }
+    uint64_t bytes() const { return b_rec + b_skey + b_mkey + b_mtail + b_mflag + b_rdx; }
+};
+
 void free_device(kad_searches* ss) {
     if (ss->rec) (void)hipFree(ss->rec);
     if (ss->skey) (void)hipFree(ss->skey);
@@ -541,16 +709,15 @@ int kad_searches_create(kad_searches** out, int device, uint32_t S, uint32_t cap
     for (uint32_t s = 0; s < S; s++) std::memcpy(&skey[s], plan.rec.data() + (size_t)s * SREC_WORDS, 8);
     // the prefix directory of large sets: rdx[p] = the number of search keys whose top B bits are below p
     std::vector<uint32_t> rdx;
-    if (S > LDS_KEYS) {
-        uint32_t B = 1;
-        while (B < 24 && (1u << B) < S) B++;
-        ss->rshift = 64 - B;
-        rdx.assign((1ull << B) + 1, 0u);
+    const Layout L(S, cap);
+    if (L.B) {
+        ss->rshift = 64 - L.B;
+        rdx.assign((1ull << L.B) + 1, 0u);
         for (uint32_t s = 0; s < S; s++) rdx[(size_t)(skey[s] >> ss->rshift) + 1]++;
         for (size_t p = 1; p < rdx.size(); p++) rdx[p] += rdx[p - 1];
     }
-    const size_t b_rec = 64ull * S, b_skey = S > LDS_KEYS ? 0 : 8ull * S, b_mkey = 8ull * S * cap, b_mtail = 12ull * S * cap,
-                 b_mflag = (size_t)S * cap, b_rdx = 4ull * rdx.size();
+    const size_t b_rec = L.b_rec, b_skey = L.b_skey, b_mkey = L.b_mkey, b_mtail = L.b_mtail, b_mflag = L.b_mflag,
+                 b_rdx = L.b_rdx;
     if (hipMalloc((void**)&ss->rec, b_rec) != hipSuccess ||
         (b_skey && hipMalloc((void**)&ss->skey, b_skey) != hipSuccess) ||
         hipMalloc((void**)&ss->mkey, b_mkey) != hipSuccess || hipMalloc((void**)&ss->mtail, b_mtail) != hipSuccess ||
@@ -611,6 +778,101 @@ int kad_searches_patch(kad_searches* ss, uint32_t m, const uint32_t* which, cons
     return KAD_OK;
 }
 
+int kad_searches_apply(kad_searches* ss, const uint32_t* erase, uint32_t n_erase, const uint8_t* ins_ids,
+                       const uint8_t* ins_flags, uint32_t n_ins, uint32_t new_cap, uint32_t* remap, uint32_t* new_index) {
+    if (!ss) return set_error(KAD_ERR_INVALID, "NULL search set");
+    if ((n_erase && !erase) || (n_ins && !ins_ids)) return set_error(KAD_ERR_INVALID, "NULL argument");
+    std::string err;
+    if (int rc = kadplan::searches_check_erase(ss->S, erase, n_erase, err)) return set_error(rc, err.c_str());
+    if (new_cap && new_cap < ss->cap) return set_error(KAD_ERR_INVALID, "new_cap below cap: slabs do not shrink");
+    for (uint32_t j = 0; ins_flags && j < n_ins; j++)
+        if (ins_flags[j] & ~KAD_SR_EXPIRED) return set_error(KAD_ERR_INVALID, "unknown search flag");
+    const uint32_t S = ss->S, cap = ss->cap, cap2 = new_cap ? new_cap : cap;
+    const bool members = n_erase || n_ins;
+    kadplan::SearchesApplyPlan plan;
+    try {
+        if (members) {
+            if (int rc = kadplan::searches_apply_plan(S, ss->h_ids.data(), erase, n_erase, ins_ids, n_ins, plan, err))
+                return set_error(rc, err.c_str());
+        } else if (cap2 != cap) {  // larger slabs alone: every search stays where it is, and so do the IDs
+            plan.src.resize(S);
+            std::iota(plan.src.begin(), plan.src.end(), 0u);
+            plan.remap = plan.src;
+        }
+    } catch (const std::bad_alloc&) {
+        return set_error(KAD_ERR_NOMEM, "searches apply: out of host memory");
+    }
+    const uint64_t S2 = (uint64_t)S - n_erase + n_ins;
+    // the limit also keeps an insert slot clear of SRC_NEW and SRC_EXPIRED in its source word (n_ins <= S' < 2^31 / cap')
+    if (S2 * cap2 >= 0x7FFFFFFFull || n_ins > SRC_SLOT) return set_error(KAD_ERR_INVALID, "search set too large");
+    if (!members && cap2 == cap) {
+        for (uint32_t s = 0; remap && s < S; s++) remap[s] = s;
+        return KAD_OK;
+    }
+    for (uint32_t j = 0; ins_flags && j < n_ins; j++)
+        if (ins_flags[j] & KAD_SR_EXPIRED) plan.src[plan.new_index[j]] |= SRC_EXPIRED;
+    DeviceGuard g(ss->device);
+    SR_HIP_TRY(hipDeviceSynchronize());  // queries enqueued before the call read the old set
+    kad_searches nw;  // the new arrays, beside the old ones until the last device step succeeded
+    const Layout L((uint32_t)S2, cap2);
+    uint8_t* scratch = nullptr;  // src, then the inserted IDs
+    auto fail = [&](int code, const char* what) {
+        (void)hipGetLastError();
+        if (scratch) (void)hipFree(scratch);
+        free_device(&nw);
+        return set_error(code, what);
+    };
+    if (S2) {
+        if (hipMalloc((void**)&nw.rec, L.b_rec) != hipSuccess ||
+            (L.b_skey && hipMalloc((void**)&nw.skey, L.b_skey) != hipSuccess) ||
+            hipMalloc((void**)&nw.mkey, L.b_mkey) != hipSuccess || hipMalloc((void**)&nw.mtail, L.b_mtail) != hipSuccess ||
+            hipMalloc((void**)&nw.mflag, L.b_mflag) != hipSuccess ||
+            (L.b_rdx && hipMalloc((void**)&nw.rdx, L.b_rdx) != hipSuccess) ||
+            hipMalloc((void**)&scratch, 4ull * S2 + 20ull * n_ins) != hipSuccess)
+            return fail(KAD_ERR_NOMEM, "searches apply: out of device memory");
+        if (hipMemcpy(scratch, plan.src.data(), 4ull * S2, hipMemcpyHostToDevice) != hipSuccess ||
+            (n_ins && hipMemcpy(scratch + 4ull * S2, ins_ids, 20ull * n_ins, hipMemcpyHostToDevice) != hipSuccess))
+            return fail(KAD_ERR_HIP, "searches apply: upload failed");
+        const DevRelayout D{reinterpret_cast<const u32x4_t*>(ss->rec), ss->mkey, ss->mtail, ss->mflag,
+                            reinterpret_cast<u32x4_t*>(nw.rec), nw.skey, nw.mkey, nw.mtail, nw.mflag,
+                            reinterpret_cast<const uint32_t*>(scratch),
+                            reinterpret_cast<const uint32_t*>(scratch + 4ull * S2), (uint32_t)S2, cap, cap2};
+        const bool wide = cap % 16 == 0 && cap2 % 16 == 0;
+        // units: 4 per record, then keys, tails and flags as the kernel counts them
+        const uint64_t e = S2 * cap2, units = 4 * S2 + (wide ? e / 2 + e / 4 * 3 + e / 16 : 2 * e + (e + 3) / 4);
+        const uint64_t blocks = (units + BLOCK - 1) / BLOCK;
+        const dim3 grid((uint32_t)(blocks < RELAYOUT_GRID ? blocks : RELAYOUT_GRID));
+        if (wide)
+            hipLaunchKernelGGL(searches_relayout_kernel<true>, grid, dim3(BLOCK), 0, nullptr, D);
+        else
+            hipLaunchKernelGGL(searches_relayout_kernel<false>, grid, dim3(BLOCK), 0, nullptr, D);
+        if (hipGetLastError() != hipSuccess) return fail(KAD_ERR_HIP, "searches apply: relayout launch failed");
+        if (L.B) {
+            const uint32_t slots = (1u << L.B) + 1;
+            hipLaunchKernelGGL(searches_rdx_kernel, dim3((slots + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr,
+                               reinterpret_cast<const u32x4_t*>(nw.rec), (uint32_t)S2, 64 - L.B, slots, nw.rdx);
+            if (hipGetLastError() != hipSuccess) return fail(KAD_ERR_HIP, "searches apply: directory launch failed");
+        }
+        if (hipDeviceSynchronize() != hipSuccess) return fail(KAD_ERR_HIP, "searches apply: relayout failed");
+        (void)hipFree(scratch);
+    }
+    free_device(ss);  // the old arrays; the new ones take their place
+    ss->rec = nw.rec;
+    ss->skey = nw.skey;
+    ss->mkey = nw.mkey;
+    ss->mtail = nw.mtail;
+    ss->mflag = nw.mflag;
+    ss->rdx = nw.rdx;
+    ss->S = (uint32_t)S2;
+    ss->cap = cap2;
+    ss->rshift = L.B ? 64 - L.B : 0;
+    ss->bytes = L.bytes();
+    if (members) ss->h_ids.swap(plan.ids);
+    if (remap && S) std::memcpy(remap, plan.remap.data(), 4ull * S);
+    if (new_index && n_ins) std::memcpy(new_index, plan.new_index.data(), 4ull * n_ins);
+    return KAD_OK;
+}
+
 int kad_searches_info(const kad_searches* ss, uint32_t* S, uint32_t* cap, uint64_t* device_bytes) {
     if (!ss) return set_error(KAD_ERR_INVALID, "NULL search set");
     if (S) *S = ss->S;
@@ -660,7 +922,7 @@ int kad_searches_export(const kad_searches* ss, uint8_t* ids, uint8_t* flags, ui
 
 int kad_searches_destroy(kad_searches* ss) {
     if (!ss) return KAD_OK;
-    if (ss->S) {
+    if (ss->S || ss->rf_ev[0]) {  // kad_searches_apply can empty a set that holds refill events
         DeviceGuard g(ss->device);
         (void)hipDeviceSynchronize();
         for (hipEvent_t e : ss->rf_ev)

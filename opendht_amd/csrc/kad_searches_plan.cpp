@@ -1,6 +1,7 @@
 // Host plan of a device search set; see kad_searches_plan.h.
 #include "kad_searches_plan.h"
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -105,6 +106,57 @@ int searches_plan(uint32_t m, uint32_t cap, const uint8_t* ids, const uint8_t* f
         r[SREC_T] = t;
         r[SREC_BITS] = (full ? SREC_FULL : 0u) | ((flags[s] & KAD_SR_EXPIRED) ? SREC_EXPIRED : 0u);
     }
+    return KAD_OK;
+}
+
+int searches_check_erase(uint32_t S, const uint32_t* erase, uint32_t n_erase, std::string& err) {
+    for (uint32_t k = 0; k < n_erase; k++)
+        if (erase[k] >= S || (k && erase[k] <= erase[k - 1]))
+            return fail(err, KAD_ERR_INVALID, "erased searches must be strictly ascending and below S (entry %u)", k);
+    return KAD_OK;
+}
+
+int searches_apply_plan(uint32_t S, const uint8_t* ids, const uint32_t* erase, uint32_t n_erase, const uint8_t* ins_ids,
+                        uint32_t n_ins, SearchesApplyPlan& out, std::string& err) {
+    if (int rc = searches_check_erase(S, erase, n_erase, err)) return rc;
+    std::vector<uint32_t> ord(n_ins);  // the insert slots in ascending ID order
+    for (uint32_t j = 0; j < n_ins; j++) ord[j] = j;
+    std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) {
+        return std::memcmp(ins_ids + 20ull * a, ins_ids + 20ull * b, KAD_HASH_LEN) < 0;
+    });
+    for (uint32_t k = 1; k < n_ins; k++)
+        if (std::memcmp(ins_ids + 20ull * ord[k - 1], ins_ids + 20ull * ord[k], KAD_HASH_LEN) == 0)
+            return fail(err, KAD_ERR_INVALID, "inserted search IDs %u and %u are equal", ord[k - 1], ord[k]);
+    const size_t S2 = (size_t)S - n_erase + n_ins;
+    out.src.clear();
+    out.src.reserve(S2);
+    out.ids.resize(20 * S2);
+    out.remap.assign(S, KAD_NO_NODE);
+    out.new_index.assign(n_ins, 0u);
+    uint32_t e = 0, k = 0;
+    auto emit = [&](const uint8_t* id, uint32_t word) {
+        std::memcpy(&out.ids[20 * out.src.size()], id, KAD_HASH_LEN);
+        out.src.push_back(word);
+    };
+    auto emit_new = [&]() {
+        out.new_index[ord[k]] = (uint32_t)out.src.size();
+        emit(ins_ids + 20ull * ord[k], SRC_NEW | ord[k]);
+        k++;
+    };
+    for (uint32_t s = 0; s < S; s++) {
+        if (e < n_erase && erase[e] == s) {
+            e++;
+            continue;
+        }
+        const uint8_t* id = ids + 20ull * s;
+        int c = 1;
+        while (k < n_ins && (c = std::memcmp(ins_ids + 20ull * ord[k], id, KAD_HASH_LEN)) < 0) emit_new();
+        if (k < n_ins && c == 0)
+            return fail(err, KAD_ERR_INVALID, "inserted search ID %u equals the kept search %u", ord[k], s);
+        out.remap[s] = (uint32_t)out.src.size();
+        emit(id, s);
+    }
+    while (k < n_ins) emit_new();
     return KAD_OK;
 }
 

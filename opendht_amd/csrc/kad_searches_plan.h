@@ -37,4 +37,23 @@ int searches_check_ids(uint32_t S, const uint8_t* ids, std::string& err);
 int searches_plan(uint32_t m, uint32_t cap, const uint8_t* ids, const uint8_t* flags, const uint32_t* off,
                   const uint8_t* node_ids, const uint8_t* node_flags, SearchesPlan& out, std::string& err);
 
+// Host plan of kad_searches_apply: the merge of the kept searches with the inserted ones.
+constexpr uint32_t SRC_NEW = 0x80000000u;  // src word of an inserted search: SRC_NEW | its slot in ins_ids
+
+struct SearchesApplyPlan {
+    std::vector<uint32_t> src;        // per new search: the old index it comes from, or SRC_NEW | insert slot
+    std::vector<uint32_t> remap;      // per old search: its new index, KAD_NO_NODE if erased
+    std::vector<uint32_t> new_index;  // per inserted search: its new index
+    std::vector<uint8_t> ids;         // the new set's IDs, S' x 20 B ascending
+};
+
+// erase[0..n_erase) strictly ascending and below S: KAD_OK or KAD_ERR_INVALID with `err` set.
+int searches_check_erase(uint32_t S, const uint32_t* erase, uint32_t n_erase, std::string& err);
+
+// ids: the set's S IDs ascending; ins_ids: n_ins x 20 B in any order. Checked in this order: the erase list
+// (searches_check_erase), then inserted IDs not distinct or one equal to a kept search's ID (KAD_ERR_INVALID; the ID
+// of a search erased by the same call is allowed). O(S + n_ins log n_ins).
+int searches_apply_plan(uint32_t S, const uint8_t* ids, const uint32_t* erase, uint32_t n_erase, const uint8_t* ins_ids,
+                        uint32_t n_ins, SearchesApplyPlan& out, std::string& err);
+
 }  // namespace kadplan

@@ -12,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (KAD_SEARCH_NODES, KAD_SR_REFILL_OVERFLOW, KAD_SR_STOP_END, KAD_SR_STOP_FAR,
+from ._lib import (KAD_NO_NODE, KAD_SEARCH_NODES, KAD_SR_REFILL_OVERFLOW, KAD_SR_STOP_END, KAD_SR_STOP_FAR,
                    KAD_SR_STOP_FAR_EXPIRED, KAD_SR_STOP_KNOWN, check, lib, ptr)
 from .table import _as_ids, _stream_of
 
@@ -92,6 +92,34 @@ class DeviceSearches:
         flags, off, node_ids, node_flags = _lists(which.shape[0], flags, off, node_ids, node_flags)
         check(lib().kad_searches_patch(self._h, which.shape[0], ptr(which), ptr(flags), ptr(off), ptr(node_ids),
                                        ptr(node_flags)), "kad_searches_patch")
+
+    def apply(self, erase=(), ins_ids=(), ins_flags=None, cap=None):
+        """Erase the searches `erase` (strictly ascending indices), insert empty searches with the IDs ins_ids
+        ((n, 20) uint8, any order; ins_flags (n,) uint8 KAD_SR_EXPIRED or None) and grow the slabs to `cap` entries
+        (None or 0 keeps them), on the device (kad_searches_apply): (remap (S,) uint32 with the new index of every old
+        search, KAD_NO_NODE if erased; new_index (n,) uint32 of the inserted ones). Synchronous."""
+        erase = np.ascontiguousarray(erase, dtype=np.uint32).reshape(-1)
+        ins = _as_ids(ins_ids) if len(ins_ids) else np.zeros((0, 20), np.uint8)
+        n_ins = ins.shape[0]
+        if ins_flags is not None:
+            ins_flags = np.ascontiguousarray(ins_flags, dtype=np.uint8).reshape(-1)
+            if ins_flags.shape[0] != n_ins:
+                raise ValueError("ins_flags must have one byte per inserted search")
+        remap, new_index = np.zeros(self.S, np.uint32), np.zeros(n_ins, np.uint32)
+        check(lib().kad_searches_apply(self._h, ptr(erase), erase.shape[0], ptr(ins), ptr(ins_flags), n_ins,
+                                       cap or 0, ptr(remap), ptr(new_index)), "kad_searches_apply")
+        kept = remap != KAD_NO_NODE
+        ids = np.zeros((int(kept.sum()) + n_ins, 20), np.uint8)
+        ids[remap[kept]] = self._ids[kept]
+        ids[new_index] = ins
+        self.S, self._ids = ids.shape[0], ids
+        if cap:  # None and 0 keep the cap
+            self.cap = cap
+        return remap, new_index
+
+    def grow(self, cap: int) -> None:
+        """Slabs of `cap` entries (>= the current cap) for the same searches: apply with the cap alone."""
+        self.apply(cap=cap)
 
     def export(self, nodes: bool = True) -> dict:
         """The device state as host arrays (kad_searches_export): ids, flags, n, full, t per search and, with
@@ -301,3 +329,25 @@ def refill_searches(DS: DeviceSearches, NC, host, which, now) -> dict:
         else:
             DS.recreate(*states(range(DS.S)), cap=max(longest, 2 * DS.cap))
     return counts
+
+
+def start_searches(DS: DeviceSearches, NC, host, new_ids, now) -> dict:
+    """Dht::search (dht.cpp:1673-1735) for a batch of new search IDs ((n, 20) uint8, distinct, none live): the host
+    emplaces the empty searches (host.add(ids); its indices follow the ascending ID order of the map), the device set
+    takes them with one DeviceSearches.apply, and refill_searches fills them from the NodeCache table NC (:1728).
+    Nothing but the IDs is uploaded. Returns refill_searches' counts plus "new_index", the index of every new search
+    in the order of new_ids."""
+    ids = _as_ids(new_ids)
+    host.add(ids)
+    _, new_index = DS.apply(ins_ids=ids)
+    counts = refill_searches(DS, NC, host, np.sort(new_index), now)
+    counts["new_index"] = new_index
+    return counts
+
+
+def expire_searches(DS: DeviceSearches, host, erase):
+    """Dht::expireSearches (dht.cpp:1060-1074) for the searches `erase` (strictly ascending indices): host.erase(erase)
+    drops them from the host's map and one DeviceSearches.apply from the device set. Returns remap."""
+    erase = np.ascontiguousarray(erase, dtype=np.uint32).reshape(-1)
+    host.erase(erase)
+    return DS.apply(erase=erase)[0]
