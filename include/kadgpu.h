@@ -591,6 +591,40 @@ int kad_sr_refill(kad_searches* ss, const kad_table* nc, uint32_t m, const uint3
  * the last kad_sr_refill on this set, in milliseconds, from two events the call records around it (0 before the first). */
 int kad_sr_refill_kernel_ms(const kad_searches* ss, float* out_ms);
 
+/* ---- Search::insertNode over a set of live searches, candidates of the caller (dht.cpp:961-1047) ---- */
+/* For each listed search s = which[i], s.insertNode(x, now, empty token) on its candidates x = entries off[i] ..
+ * off[i+1] of cand_ids, in list order, with node identity = ID: found, trim, insert, flip, pops and erase exactly as
+ * spelled out above kad_sr_refill (the trim cuts the list even when the candidate is then refused), and, because a
+ * candidate may be expired (cand_flags & KAD_SN_BAD = node->isExpired()):
+ *   - the new entry's flag byte is cand_flags & KAD_SN_BAD; it never carries KAD_SN_REMOVABLE (node.time = now precedes
+ *     removeExpiredNode);
+ *   - on an expired search a candidate that is not BAD flips it to live and nothing is popped (:1026-1029); a BAD
+ *     candidate does not flip it: `bad` stays 0 and the pop loop cuts the list to 14 entries;
+ *   - on a live search the pop loop stops at the 15th entry that is not BAD, a BAD candidate counting as bad.
+ * The same ID may appear twice in one list: the second occurrence is found and answers 0. Afterwards the record and
+ * slab of s are what kad_searches_create derives from the new list (n, t, full, the threshold, KAD_SR_EXPIRED, zeros
+ * past n). The KAD_SN_REMOVABLE bits of the set are the caller's, evaluated at the call's `now`; a candidate whose own
+ * node is removable at `now` and a member of another search is the caller's to order (its node.time = now clears that
+ * bit there).
+ * A search whose list would hold more than cap entries after some insertNode returns gets KAD_SR_INSERT_OVERFLOW, is
+ * left byte for byte as it was, and all its out_inserted bytes are 0; the other searches of the call are unaffected.
+ * Host arrays, synchronous; as kad_sr_refill towards queries (it first waits for all device work enqueued before the
+ * call). which: m search indices, strictly ascending, < S. off: m + 1 CSR offsets, off[0] == 0, not descending; an
+ * empty list leaves its search untouched with status OK. cand_ids: 20 bytes per candidate. cand_flags: one byte per
+ * candidate, only KAD_SN_BAD, NULL = all zero. out_inserted: one byte per candidate, 1 if that insertNode returned
+ * true. out_status: one byte per listed search. Checked in this order, before any device work, every failure leaving
+ * the set unchanged: NULL ss; NULL which / off / out_status with m > 0; NULL cand_ids / out_inserted with off[m] > 0;
+ * which not strictly ascending or not < S; off[0] != 0, off descending or off[m] >= 0x7FFFFFFF; a flag byte with bits
+ * other than KAD_SN_BAD (all KAD_ERR_INVALID); m == 0 (KAD_OK); cap > 64 (KAD_ERR_UNSUPPORTED). One wave per search,
+ * one list entry per lane; the scratch is allocated per call. */
+#define KAD_SR_INSERT_OK 0u
+#define KAD_SR_INSERT_OVERFLOW 1u
+int kad_sr_insert(kad_searches* ss, uint32_t m, const uint32_t* which, const uint32_t* off, const uint8_t* cand_ids,
+                  const uint8_t* cand_flags, uint8_t* out_inserted, uint8_t* out_status);
+/* Measurement aid (tools/sr_insert_bench.py), as kad_sr_refill_kernel_ms: the device time of the insert kernel of the
+ * last kad_sr_insert on this set, in milliseconds (0 before the first). */
+int kad_sr_insert_kernel_ms(const kad_searches* ss, float* out_ms);
+
 /* Per-query family select for NodeCache::getCachedNodes(id, sa_family, count) (node_cache.cpp:36-66:
  * cache_4 or cache_6 by family; Dht::refill asks the search's family, dht.cpp:1650): af[i] = 0 -> table4,
  * 1 -> table6 (KAD_TABLE_SORTED tables; either may be NULL = an empty map). Any count (as kad_nc_closest_batch).

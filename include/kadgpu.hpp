@@ -828,6 +828,15 @@ struct RefillResult {
     bool overflow;  // handed back: the host's walk stands and sync() overwrites the device copy
 };
 
+/* One search's inserts on the device (SearchesMirror::insertBatch): inserted[j] = insertNode(nodes[j], now) returned
+ * true on the device copy, and overflow = the device copy was not touched (its list outgrew the slab, or one of its
+ * candidates is removable at `now`): the host's own insertNode loop stands, and the search is reported to sync(). As
+ * for RefillResult, read overflow as "handed back to the host". */
+struct InsertResult {
+    std::vector<uint8_t> inserted;
+    bool overflow;
+};
+
 /* Device mirror of one family's live searches (Dht::searches(af), dht.h) over a map shaped like
  * std::map<InfoHash, std::shared_ptr<Search>>. Reads of a search: id, expired, nodes[i].node->id, nodes[i].isBad().
  * The map must outlive the mirror or the next snapshot. */
@@ -983,6 +992,71 @@ public:
         }
         for (auto& r : out)
             if (r.overflow) r.inserted = 0;
+        return out;
+    }
+
+    /* sr.insertNode(n, now) with an empty token for every node n of nodes[i], in order, on the search ids[i] (distinct,
+     * mirrored), on the device: one kad_sr_insert, KAD_SN_BAD = n->isExpired(). As refillBatch, the listed searches
+     * whose KAD_SN_REMOVABLE bits at `now` differ from the mirrored ones are patched first (same precondition), and the
+     * host then runs the same insertNode calls on its own searches and reports the searches with overflow set to
+     * sync(changed, now). A search with a candidate that is removable at `now` is not sent and comes back with overflow
+     * set: insertNode's node.time = now clears that node's REMOVABLE bit in every search that holds it, so the host's
+     * walk stands and those searches go through sync() too. Results in the order of `ids`. */
+    template <class InfoHashT, class NodePtrT, class TimePoint>
+    std::vector<InsertResult> insertBatch(const std::vector<InfoHashT>& ids,
+                                          const std::vector<std::vector<NodePtrT>>& nodes, TimePoint now) {
+        if (ids.size() != nodes.size()) throw Error(KAD_ERR_INVALID, "SearchesMirror::insertBatch: one node list per search");
+        std::vector<InsertResult> out(ids.size());
+        if (ids.empty()) return out;
+        if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::insertBatch before snapshot");
+        const uint32_t m = (uint32_t)ids.size();
+        std::vector<std::pair<uint32_t, uint32_t>> order(m);  // (search index, position in ids)
+        for (uint32_t i = 0; i < m; i++) order[i] = std::make_pair(index_of(id_bytes(ids[i])), i);
+        std::sort(order.begin(), order.end());
+        for (uint32_t k = 1; k < m; k++)
+            if (order[k].first == order[k - 1].first)
+                throw Error(KAD_ERR_INVALID, "SearchesMirror::insertBatch: a search listed twice");
+        const At<TimePoint> when{now};
+        std::vector<uint32_t> which, off(1, 0u), pos;  // the searches that are sent, and their positions in ids
+        std::vector<uint8_t> cid, cfl;
+        std::vector<InfoHashT> moved;
+        {
+            auto it = map_->begin();
+            uint32_t at = 0;
+            for (uint32_t k = 0; k < m; k++) {
+                const uint32_t i = order[k].second;
+                out[i].inserted.assign(nodes[i].size(), 0);
+                out[i].overflow = false;
+                for (const auto& n : nodes[i]) out[i].overflow = out[i].overflow || when.removable(*n);
+                if (out[i].overflow) continue;
+                std::advance(it, order[k].first - at);
+                at = order[k].first;
+                if (it == map_->end() || std::memcmp(id_bytes(it->first), &ids_[(size_t)at * KAD_HASH_LEN], KAD_HASH_LEN) != 0)
+                    throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
+                bool differ = false;  // the REMOVABLE bits moved since the search was uploaded
+                for (const auto& sn : it->second->nodes)
+                    differ = differ || when.removable(*sn.node) != (at_[at] != INT64_MIN && when.removableAt(*sn.node, at_[at]));
+                if (differ) moved.push_back(ids[i]);
+                which.push_back(at);
+                pos.push_back(i);
+                for (const auto& n : nodes[i]) {
+                    cid.insert(cid.end(), id_bytes(n->id), id_bytes(n->id) + KAD_HASH_LEN);
+                    cfl.push_back(n->isExpired() ? (uint8_t)KAD_SN_BAD : (uint8_t)0);
+                }
+                off.push_back((uint32_t)cfl.size());
+            }
+        }
+        if (which.empty()) return out;
+        if (!moved.empty()) syncAt(moved, when);
+        std::vector<uint8_t> ins(cfl.size()), st(which.size());
+        check(kad_sr_insert(ss_, (uint32_t)which.size(), which.data(), off.data(), cid.data(), cfl.data(), ins.data(),
+                            st.data()), "kad_sr_insert");
+        for (size_t k = 0; k < which.size(); k++) {
+            InsertResult& r = out[pos[k]];
+            r.overflow = st[k] != KAD_SR_INSERT_OK;
+            if (!r.overflow) r.inserted.assign(ins.begin() + off[k], ins.begin() + off[k + 1]);
+            at_[which[k]] = when.ns();
+        }
         return out;
     }
 
@@ -1224,6 +1298,13 @@ public:
     std::vector<RefillResult<typename NodeCacheFamilyMirror<NodeMapT>::NodePtr>>
     refillBatch(const NodeCacheMirror<NodeMapT>& cache, sa_family_t af, const std::vector<InfoHashT>& ids) {
         return searches(af).refillBatch(cache.family(af), ids, clock_());
+    }
+    /* Search::insertNode of the nodes nodes[i] into the search ids[i] of one family, at the mirror's clock
+     * (SearchesMirror::insertBatch); syncSearches(af, changed, now) reports the ones handed back. */
+    template <class InfoHashT, class NodePtrT>
+    std::vector<InsertResult> insertBatch(sa_family_t af, const std::vector<InfoHashT>& ids,
+                                          const std::vector<std::vector<NodePtrT>>& nodes) {
+        return searches(af).insertBatch(ids, nodes, clock_());
     }
     template <class InfoHashT>
     void syncSearches(sa_family_t af, const std::vector<InfoHashT>& changed, time_point now) {

@@ -14,9 +14,11 @@ from ._lib import (KAD_NN_BOOTSTRAP, KAD_NN_FULL, KAD_NN_INSERT, KAD_NN_KIND_MAS
 from ._lib import (KAD_SN_BAD, KAD_SR_EXPIRED, KAD_SR_STOP_END, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED,
                    KAD_SR_STOP_KNOWN)
 from ._lib import KAD_SN_REMOVABLE, KAD_SR_REFILL_OK, KAD_SR_REFILL_OVERFLOW
+from ._lib import KAD_SR_INSERT_OK, KAD_SR_INSERT_OVERFLOW
 from ._lib import KAD_SWEEP_INCOMING
 from .ingest import ingest
-from .searches import DeviceSearches, expire_searches, refill_searches, start_searches, try_search_insert
+from .searches import (DeviceSearches, expire_searches, plan_insert_round, refill_searches, start_searches,
+                       try_search_insert, try_search_insert_device)
 from .table import DeviceTable, nc_closest_dual, rt_closest_dual, rt_responsible_dual
 
 __all__ = [
@@ -29,4 +31,5 @@ __all__ = [
     "KAD_SR_STOP_KNOWN", "DeviceSearches", "try_search_insert", "KAD_SWEEP_INCOMING",
     "KAD_SN_REMOVABLE", "KAD_SR_REFILL_OK", "KAD_SR_REFILL_OVERFLOW", "refill_searches",
     "start_searches", "expire_searches",
+    "KAD_SR_INSERT_OK", "KAD_SR_INSERT_OVERFLOW", "plan_insert_round", "try_search_insert_device",
 ]

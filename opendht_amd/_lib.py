@@ -41,6 +41,7 @@ KAD_NN_KIND_MASK, KAD_NN_MYBUCKET, KAD_NN_BOOTSTRAP = 0x0F, 0x10, 1
 KAD_SR_EXPIRED, KAD_SN_BAD = 0x01, 0x01
 KAD_SN_REMOVABLE = 0x02
 KAD_SR_REFILL_OK, KAD_SR_REFILL_OVERFLOW = 0, 1
+KAD_SR_INSERT_OK, KAD_SR_INSERT_OVERFLOW = 0, 1
 KAD_SR_STOP_END, KAD_SR_STOP_KNOWN, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED = 0, 1, 2, 3
 KAD_SWEEP_INCOMING = 1
 
@@ -154,6 +155,8 @@ SIGNATURES = {
     "kad_sr_try_insert_batch_host": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P]),
     "kad_sr_refill": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
     "kad_sr_refill_kernel_ms": (C.c_int, [_P, _P]),
+    "kad_sr_insert": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    "kad_sr_insert_kernel_ms": (C.c_int, [_P, _P]),
     "kad_rt_shard_batch": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
                                      _P, _P]),

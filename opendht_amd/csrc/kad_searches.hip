@@ -21,6 +21,10 @@
 // of the listed searches, then Search::insertNode on every row node in walk order, applied to the slabs and records
 // in place by refill_kernel, one wave per search with one list entry per lane.
 //
+// kad_sr_insert is Search::insertNode on candidates of the caller, any number per listed search and
+// each with its own KAD_SN_BAD bit, applied in place by insert_kernel in the same one-wave-per-search form: the accepted
+// inserts of a trySearchInsert tick without an upload of the touched lists.
+//
 // kad_searches_apply changes the membership (Dht::search dht.cpp:1673-1735, Dht::expireSearches
 // :1060-1074) and the slab size: the host plans one source word per new search, searches_relayout_kernel gathers the
 // records and slabs into new arrays beside the old ones, searches_rdx_kernel rebuilds the prefix directory, and the
@@ -40,7 +44,7 @@
 
 // tests/test_refill_abi.py, test_searches_abi.py and test_searches_apply_abi.py hand the argument checks a zeroed
 // buffer for a set: it must read as a set of no searches (S == 0, cap == 0, no pointer followed before the checks end,
-// rf_ms == 0).
+// rf_ms == 0); tests/test_sr_insert_abi.py does the same (in_ms == 0).
 struct kad_searches {
     int device = 0;
     uint32_t S = 0, cap = 0;
@@ -55,6 +59,8 @@ struct kad_searches {
     std::vector<uint8_t> h_ids;  // S x 20: a patch checks its lists against the search IDs
     hipEvent_t rf_ev[2] = {nullptr, nullptr};  // around the last kad_sr_refill's refill kernel
     float rf_ms = 0.f;
+    hipEvent_t in_ev[2] = {nullptr, nullptr};  // around the last kad_sr_insert's insert kernel
+    float in_ms = 0.f;
 };
 
 namespace {
@@ -481,6 +487,165 @@ __global__ __launch_bounds__(BLOCK) void refill_kernel(DevRefill D, const uint32
         out_ins[i] = overflow ? (uint16_t)0 : (uint16_t)ins;
         out_status[i] = overflow ? (uint8_t)KAD_SR_REFILL_OVERFLOW : (uint8_t)KAD_SR_REFILL_OK;
     }
+}
+
+// ---- kad_sr_insert: Search::insertNode on candidates of the caller --------------------------------
+// refill_kernel's insert step for any number of candidates per search, each with its own KAD_SN_BAD bit: one wave per
+// listed search, one list entry per lane, the candidates of search which[i] at off[i] .. off[i+1] of the uploaded CSR.
+// They are loaded one per lane, 64 at a time, the next chunk's loads issued before the current chunk's inserts; the
+// candidate of a step is broadcast from its lane (v_readlane with a wave-uniform lane number).
+struct DevInsert {
+    uint32_t* rec;
+    uint64_t* mkey;
+    uint32_t* mtail;
+    uint8_t* mflag;
+    uint32_t cap, m;
+    const uint32_t* which;  // m
+    const uint32_t* off;    // m + 1
+    const uint8_t* ids;     // off[m] x 20 B
+    const uint8_t* flags;   // off[m]
+    uint8_t* out_ins;       // off[m]
+    uint8_t* out_status;    // m
+};
+
+// candidate `at` of [.., end) as an entry of the search with ID words s0..s4 (load_cand's byte order): its XOR distance
+// and KAD_SN_BAD; zero past the end
+__device__ __forceinline__ Ent load_cand_ent(const DevInsert& D, uint32_t at, uint32_t end, uint32_t s0, uint32_t s1,
+                                             uint32_t s2, uint32_t s3, uint32_t s4) {
+    Ent c = {};
+    if (at < end) {
+        const Cand x = load_cand(D.ids, at);
+        c = Ent{(uint32_t)x.hi ^ s0, (uint32_t)(x.hi >> 32) ^ s1, x.t2 ^ s2, x.t3 ^ s3, x.t4 ^ s4,
+                (uint32_t)__builtin_nontemporal_load(D.flags + at) & KAD_SN_BAD};
+    }
+    return c;
+}
+
+__global__ __launch_bounds__(BLOCK) void insert_kernel(DevInsert D) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t i = rfl(blockIdx.x * REFILL_WAVES + (threadIdx.x >> 6));
+    if (i >= D.m) return;
+    const uint32_t s = rfl(D.which[i]), a = rfl(D.off[i]), b = rfl(D.off[i + 1]);
+    if (a >= b) {  // an empty list: the search is untouched
+        if (lane == 0) D.out_status[i] = (uint8_t)KAD_SR_INSERT_OK;
+        return;
+    }
+    // the record, the slab and the first chunk of candidates: all loads in flight together
+    uint32_t* r = D.rec + (uint64_t)SREC_WORDS * s;
+    const uint32_t s0 = rfl(r[0]), s1 = rfl(r[1]), s2 = rfl(r[2]), s3 = rfl(r[3]), s4 = rfl(r[4]);
+    uint32_t n = min(rfl(r[SREC_N]), D.cap);
+    bool expired = (rfl(r[SREC_BITS]) & SREC_EXPIRED) != 0;
+    const uint64_t e0 = (uint64_t)s * D.cap + lane;
+    Ent e = {};
+    if (lane < n) {
+        const uint64_t k = D.mkey[e0];
+        const uint32_t* tl = D.mtail + 3ull * e0;
+        e = Ent{(uint32_t)k ^ s0, (uint32_t)(k >> 32) ^ s1, tl[0] ^ s2, tl[1] ^ s3, tl[2] ^ s4, D.mflag[e0]};
+    }
+    Ent c = load_cand_ent(D, a + lane, b, s0, s1, s2, s3, s4);
+
+    bool dirty = false, overflow = false;
+    // Lanes at or beyond n hold stale entries by design, as in refill_kernel: every ballot masks with lane < n.
+    for (uint32_t base = a; base < b && !overflow; base += 64u) {
+        const uint32_t cnt = min(b - base, 64u);
+        const Ent nx = load_cand_ent(D, base + 64u + lane, b, s0, s1, s2, s3, s4);  // in flight during the inserts
+        uint64_t insm = 0;
+        for (uint32_t j = 0; j < cnt; j++) {  // s.insertNode(x, now), dht.cpp:961-1047
+            const Ent x = ent_of_lane(c, j);
+            const bool valid = lane < n;  // n <= cap here
+            if (__ballot(valid && ent_same(e, x))) continue;  // found (:972-984), a repeated candidate included
+            const uint32_t pos = (uint32_t)__popcll(__ballot(valid && ent_closer(e, x)));
+            bool full;
+            uint32_t t;
+            wave_trim(expired, n, __ballot(valid && !(e.fl & KAD_SN_BAD)), lane, full, t);
+            if (full) {  // :1009-1013
+                if (t < n) {
+                    n = t;
+                    dirty = true;
+                }
+                if (pos >= t) continue;
+            }
+            // insert at pos; a list of cap = 64 entries holds its 65th, wave-uniform, until the pops and the erase
+            Ent sp = {};
+            bool has_sp = false;
+            const Ent up = ent_from(e, (lane - 1u) & 63u);
+            if (n == 64u) {
+                sp = pos == 64u ? x : ent_of_lane(e, 63u);
+                has_sp = true;
+            }
+            if (lane == pos)
+                e = x;
+            else if (lane > pos)
+                e = up;
+            n++;
+            dirty = true;
+            if (expired) {
+                if (x.fl & KAD_SN_BAD)  // bad stays 0 and the search expired: the pops cut to SEARCH_NODES entries
+                    n = min(n, KAD_SEARCH_NODES);
+                else  // a good node revives the search; bad = size - 1, so nothing is popped (:1026-1029)
+                    expired = false;
+            } else {  // the pop loop (:1031-1035): back to the 15th entry that is not BAD, the new one counted
+                const uint64_t goodm = __ballot(lane < min(n, 64u) && !(e.fl & KAD_SN_BAD));
+                const uint32_t g = (uint32_t)__popcll(goodm);
+                if (g > KAD_SEARCH_NODES)
+                    n = fifteenth_good(goodm, lane, n);
+                else if (has_sp && g == KAD_SEARCH_NODES && !(sp.fl & KAD_SN_BAD))
+                    n = 64u;
+            }
+            if (n <= 64u) has_sp = false;
+            // removeExpiredNode (dht.h:628-640): the REMOVABLE entry with the greatest index; never the new one, whose
+            // node.time = now comes first
+            const uint64_t rm = __ballot(lane < min(n, 64u) && (e.fl & KAD_SN_REMOVABLE));
+            if (has_sp && (sp.fl & KAD_SN_REMOVABLE)) {
+                n = 64u;
+                has_sp = false;
+            } else if (rm) {
+                const uint32_t at = 63u - (uint32_t)__builtin_clzll(rm);
+                Ent dn = ent_from(e, (lane + 1u) & 63u);
+                if (has_sp && lane == 63u) dn = sp;
+                if (lane >= at) e = dn;
+                n--;
+                has_sp = false;
+            }
+            insm |= 1ull << j;
+            if (n > D.cap) {
+                overflow = true;
+                break;
+            }
+        }
+        if (!overflow && lane < cnt) __builtin_nontemporal_store((uint8_t)((insm >> lane) & 1ull), D.out_ins + base + lane);
+        c = nx;
+    }
+    if (overflow)  // the search stays as it was: every result byte of its list is 0
+        for (uint32_t at = a + lane; at < b; at += 64u) __builtin_nontemporal_store((uint8_t)0, D.out_ins + at);
+
+    if (dirty && !overflow) {  // the slab and the record as kad_searches_create derives them from the new list
+        const bool in = lane < n;
+        if (lane < D.cap) {
+            D.mkey[e0] = in ? ((uint64_t)(e.k1 ^ s1) << 32) | (e.k0 ^ s0) : 0ull;
+            uint32_t* tl = D.mtail + 3ull * e0;
+            tl[0] = in ? e.d2 ^ s2 : 0u;
+            tl[1] = in ? e.d3 ^ s3 : 0u;
+            tl[2] = in ? e.d4 ^ s4 : 0u;
+            D.mflag[e0] = in ? (uint8_t)e.fl : (uint8_t)0;
+        }
+        bool full;
+        uint32_t t;
+        wave_trim(expired, n, __ballot(in && !(e.fl & KAD_SN_BAD)), lane, full, t);
+        if (lane + 1u == t || (t == 0 && lane == 0)) {  // the threshold entry[t-1], zero for t == 0
+            r[SREC_THR] = t ? e.k0 ^ s0 : 0u;
+            r[SREC_THR + 1] = t ? e.k1 ^ s1 : 0u;
+            r[SREC_THR + 2] = t ? e.d2 ^ s2 : 0u;
+            r[SREC_THR + 3] = t ? e.d3 ^ s3 : 0u;
+            r[SREC_THR + 4] = t ? e.d4 ^ s4 : 0u;
+        }
+        if (lane == 0) {
+            r[SREC_N] = n;
+            r[SREC_T] = t;
+            r[SREC_BITS] = (full ? SREC_FULL : 0u) | (expired ? SREC_EXPIRED : 0u);
+        }
+    }
+    if (lane == 0) D.out_status[i] = overflow ? (uint8_t)KAD_SR_INSERT_OVERFLOW : (uint8_t)KAD_SR_INSERT_OK;
 }
 
 // ---- kad_searches_apply: add and erase searches, grow the slabs -----------------------------------
@@ -922,10 +1087,12 @@ int kad_searches_export(const kad_searches* ss, uint8_t* ids, uint8_t* flags, ui
 
 int kad_searches_destroy(kad_searches* ss) {
     if (!ss) return KAD_OK;
-    if (ss->S || ss->rf_ev[0]) {  // kad_searches_apply can empty a set that holds refill events
+    if (ss->S || ss->rf_ev[0] || ss->in_ev[0]) {  // kad_searches_apply can empty a set that holds timing events
         DeviceGuard g(ss->device);
         (void)hipDeviceSynchronize();
         for (hipEvent_t e : ss->rf_ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ss->in_ev)
             if (e) (void)hipEventDestroy(e);
         free_device(ss);
     }
@@ -1013,6 +1180,74 @@ int kad_sr_refill(kad_searches* ss, const kad_table* nc, uint32_t m, const uint3
 int kad_sr_refill_kernel_ms(const kad_searches* ss, float* out_ms) {
     if (!ss || !out_ms) return set_error(KAD_ERR_INVALID, "NULL argument");
     *out_ms = ss->rf_ms;
+    return KAD_OK;
+}
+
+int kad_sr_insert(kad_searches* ss, uint32_t m, const uint32_t* which, const uint32_t* off, const uint8_t* cand_ids,
+                  const uint8_t* cand_flags, uint8_t* out_inserted, uint8_t* out_status) {
+    if (!ss) return set_error(KAD_ERR_INVALID, "NULL search set");
+    if (m && (!which || !off || !out_status)) return set_error(KAD_ERR_INVALID, "NULL argument");
+    if (m && off[m] > 0 && (!cand_ids || !out_inserted)) return set_error(KAD_ERR_INVALID, "NULL candidate arrays");
+    std::string err;
+    if (int rc = kadplan::sr_insert_check(ss->S, m, which, off, cand_flags, err)) return set_error(rc, err.c_str());
+    if (m == 0) return KAD_OK;
+    if (ss->cap > REFILL_MAX_CAP)
+        return set_error(KAD_ERR_UNSUPPORTED, "kad_sr_insert handles slabs of up to 64 entries");
+    const size_t T = off[m];
+    // the call's scratch, one allocation: which, off, the candidate IDs and flags as one upload, then the result bytes
+    // and the statuses as one copy back
+    const size_t o_off = 4ull * m, o_ids = o_off + 4ull * (m + 1), o_fl = o_ids + 20ull * T, o_ins = o_fl + T,
+                 o_st = o_ins + T, total = o_st + m;
+    uint8_t* h = new (std::nothrow) uint8_t[total];
+    if (!h) return set_error(KAD_ERR_NOMEM, "insert: out of host memory");
+    std::memcpy(h, which, 4ull * m);
+    std::memcpy(h + o_off, off, 4ull * (m + 1));
+    if (T) std::memcpy(h + o_ids, cand_ids, 20ull * T);
+    if (T && cand_flags)
+        std::memcpy(h + o_fl, cand_flags, T);
+    else
+        std::memset(h + o_fl, 0, T);
+    DeviceGuard g(ss->device);
+    uint8_t* buf = nullptr;
+    auto done = [&](int r) {
+        if (buf) (void)hipFree(buf);
+        delete[] h;
+        return r;
+    };
+    if (hipDeviceSynchronize() != hipSuccess)  // queries enqueued before the call read the old set
+        return done(set_error(KAD_ERR_HIP, "insert: device in error"));
+    if (hipMalloc((void**)&buf, total) != hipSuccess) {
+        (void)hipGetLastError();
+        buf = nullptr;
+        return done(set_error(KAD_ERR_NOMEM, "insert: out of device memory"));
+    }
+    if (!ss->in_ev[0] && (hipEventCreate(&ss->in_ev[0]) != hipSuccess || hipEventCreate(&ss->in_ev[1]) != hipSuccess))
+        return done(set_error(KAD_ERR_HIP, "insert: no events"));
+    if (hipMemcpy(buf, h, o_ins, hipMemcpyHostToDevice) != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, "insert: H2D failed"));
+    const DevInsert D{ss->rec, ss->mkey, ss->mtail, ss->mflag, ss->cap, m, (const uint32_t*)buf,
+                      (const uint32_t*)(buf + o_off), buf + o_ids, buf + o_fl, buf + o_ins, buf + o_st};
+    (void)hipEventRecord(ss->in_ev[0], nullptr);
+    hipLaunchKernelGGL(insert_kernel, dim3((m + REFILL_WAVES - 1) / REFILL_WAVES), dim3(BLOCK), 0, nullptr, D);
+    const hipError_t le = hipGetLastError();
+    (void)hipEventRecord(ss->in_ev[1], nullptr);
+    if (le != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, (std::string("insert: launch failed: ") + hipGetErrorString(le)).c_str()));
+    const hipError_t ce = hipMemcpy(h + o_ins, buf + o_ins, total - o_ins, hipMemcpyDeviceToHost);
+    if (ce != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, (std::string("insert: D2H failed: ") + hipGetErrorString(ce)).c_str()));
+    if (hipEventElapsedTime(&ss->in_ms, ss->in_ev[0], ss->in_ev[1]) != hipSuccess) {
+        (void)hipGetLastError();
+        ss->in_ms = 0.f;
+    }
+    if (T) std::memcpy(out_inserted, h + o_ins, T);
+    std::memcpy(out_status, h + o_st, m);
+    return done(KAD_OK);
+}
+
+int kad_sr_insert_kernel_ms(const kad_searches* ss, float* out_ms) {
+    if (!ss || !out_ms) return set_error(KAD_ERR_INVALID, "NULL argument");
+    *out_ms = ss->in_ms;
     return KAD_OK;
 }
 

@@ -160,6 +160,22 @@ int searches_apply_plan(uint32_t S, const uint8_t* ids, const uint32_t* erase, u
     return KAD_OK;
 }
 
+int sr_insert_check(uint32_t S, uint32_t m, const uint32_t* which, const uint32_t* off, const uint8_t* cand_flags,
+                    std::string& err) {
+    if (m == 0) return KAD_OK;
+    for (uint32_t k = 0; k < m; k++)
+        if (which[k] >= S || (k && which[k] <= which[k - 1]))
+            return fail(err, KAD_ERR_INVALID, "listed searches must be strictly ascending and below S (entry %u)", k);
+    if (off[0] != 0) return fail(err, KAD_ERR_INVALID, "candidate offsets must start at 0");
+    for (uint32_t k = 0; k < m; k++)
+        if (off[k + 1] < off[k]) return fail(err, KAD_ERR_INVALID, "candidate offsets not ascending at %u", k);
+    if (off[m] >= 0x7FFFFFFFu) return fail(err, KAD_ERR_INVALID, "too many candidates");
+    for (uint32_t j = 0; cand_flags && j < off[m]; j++)
+        if (cand_flags[j] & ~KAD_SN_BAD)
+            return fail(err, KAD_ERR_INVALID, "candidate %u: only KAD_SN_BAD may be set", j);
+    return KAD_OK;
+}
+
 }  // namespace kadplan
 
 extern "C" int kad_search_trim(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t* full,

@@ -56,4 +56,10 @@ int searches_check_erase(uint32_t S, const uint32_t* erase, uint32_t n_erase, st
 int searches_apply_plan(uint32_t S, const uint8_t* ids, const uint32_t* erase, uint32_t n_erase, const uint8_t* ins_ids,
                         uint32_t n_ins, SearchesApplyPlan& out, std::string& err);
 
+// The list checks of kad_sr_insert, in this order: which[0..m) not strictly ascending or not below S;
+// off[0] != 0, off descending or off[m] >= 0x7FFFFFFF; a byte of cand_flags[0..off[m]) (NULL: all zero) with bits other
+// than KAD_SN_BAD. KAD_OK or KAD_ERR_INVALID with `err` set. m == 0 reads nothing.
+int sr_insert_check(uint32_t S, uint32_t m, const uint32_t* which, const uint32_t* off, const uint8_t* cand_flags,
+                    std::string& err);
+
 }  // namespace kadplan

@@ -4,7 +4,8 @@ Dht::trySearchInsert(node) (dht.cpp:816-849) takes lower_bound(node->id) in the 
 Search::insertNode forwards and backwards until the first search that refuses. kad_sr_try_insert_batch gives, for a
 whole tick of candidates and one snapshot of the searches, which searches would take each candidate and why each
 walk stopped; try_search_insert turns those verdicts into the exact sequential result while the host touches only
-the searches that accept.
+the searches that accept. try_search_insert_device goes one step further: the accepted inserts
+run on the device as well (kad_sr_insert), in rounds planned by plan_insert_round, and no list is uploaded.
 """
 from __future__ import annotations
 
@@ -12,8 +13,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (KAD_NO_NODE, KAD_SEARCH_NODES, KAD_SR_REFILL_OVERFLOW, KAD_SR_STOP_END, KAD_SR_STOP_FAR,
-                   KAD_SR_STOP_FAR_EXPIRED, KAD_SR_STOP_KNOWN, check, lib, ptr)
+from ._lib import (KAD_NO_NODE, KAD_SEARCH_NODES, KAD_SN_BAD, KAD_SR_INSERT_OVERFLOW, KAD_SR_REFILL_OVERFLOW,
+                   KAD_SR_STOP_END, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED, KAD_SR_STOP_KNOWN, check, lib, ptr)
 from .table import _as_ids, _stream_of
 
 STOP_NAMES = {KAD_SR_STOP_END: "end", KAD_SR_STOP_KNOWN: "known", KAD_SR_STOP_FAR: "far",
@@ -178,6 +179,33 @@ class DeviceSearches:
               "kad_sr_refill")
         return rows, cnt, ins, status
 
+    def insert(self, which, off, cand_ids, cand_flags=None):
+        """Search::insertNode of the candidates cand_ids[off[i]:off[i+1]] ((T, 20) uint8, in list order; cand_flags
+        (T,) uint8 KAD_SN_BAD = node->isExpired(), None for all zero) into search which[i] (strictly ascending
+        indices), on the device (kad_sr_insert): (inserted (T,) uint8 with 1 where insertNode returned true, status
+        (m,) uint8 KAD_SR_INSERT_*). Synchronous."""
+        which = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
+        off = np.ascontiguousarray(off, dtype=np.uint32).reshape(-1)
+        m = which.shape[0]
+        if off.shape[0] != m + 1:
+            raise ValueError("off must have one offset (plus one) per listed search")
+        T = int(off[-1])
+        cand = _as_ids(cand_ids) if T else np.zeros((0, 20), np.uint8)
+        if cand_flags is not None:
+            cand_flags = np.ascontiguousarray(cand_flags, dtype=np.uint8).reshape(-1)
+        if cand.shape[0] < T or (cand_flags is not None and cand_flags.shape[0] < T):
+            raise ValueError("cand_ids / cand_flags shorter than off[-1]")
+        ins, status = np.zeros(T, np.uint8), np.zeros(m, np.uint8)
+        check(lib().kad_sr_insert(self._h, m, ptr(which), ptr(off), ptr(cand), ptr(cand_flags), ptr(ins), ptr(status)),
+              "kad_sr_insert")
+        return ins, status
+
+    def insert_kernel_ms(self) -> float:
+        """The device time of the last insert's insert kernel (kad_sr_insert_kernel_ms)."""
+        ms = C.c_float()
+        check(lib().kad_sr_insert_kernel_ms(self._h, C.byref(ms)), "kad_sr_insert_kernel_ms")
+        return ms.value
+
     @property
     def refill_kernel_ms(self) -> float:
         """The device time of the last refill's refill kernel (kad_sr_refill_kernel_ms)."""
@@ -275,6 +303,194 @@ def try_search_insert(DS: DeviceSearches, host, cand_ids) -> dict:
             DS.patch(which, flags, off, nid, nfl)
         else:  # a list outgrew the slabs (bad nodes do not count towards SEARCH_NODES): a new set
             DS.recreate(*states(range(DS.S)), cap=max(longest, 2 * DS.cap))
+    return counts
+
+
+def plan_insert_round(S: int, lb, fwd, back, stop, trims):
+    """One scan over the remaining candidates of a tick, in order, against the verdicts (host arrays) of one snapshot
+    (DESIGN.md §7.16). trims[s]: search s held entries past its trim position in the snapshot (full and t < n).
+    Returns (skipped, ready, deferred): skipped and deferred are lists of candidate positions, ready a list of
+    (position, [(search, expected insertNode result), ...]).
+
+    T_j, the searches candidate j probes, is [lb-back-1, lb+fwd] without the ends whose stop is END.
+      skipped   fwd + back == 0, both stops END or FAR, neither stopper trims: final in any order, marks nothing.
+      ready     T_j meets no T of an earlier candidate of the scan that was not skipped, and does not lie in the
+                open side of an earlier deferred one: a deferred candidate whose forward stop is KNOWN or FAR_EXPIRED
+                (stops that do not survive earlier inserts) may walk on, so it blocks every search from its lowest
+                probed index upwards; likewise backwards from its highest probed index downwards.
+      deferred  everything else; it waits for the next round.
+    The pairs of a ready candidate are its accepting searches (expected 1) and every FAR / FAR_EXPIRED stopper that
+    trims (expected 0: the refusal still cuts the list). Ready candidates of one round never share a search."""
+    far, open_stops = (KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED), (KAD_SR_STOP_KNOWN, KAD_SR_STOP_FAR_EXPIRED)
+    marked = np.zeros(S + 1, dtype=bool)
+    block_up, block_down = S, -1  # searches >= block_up and <= block_down are blocked
+    skipped, ready, deferred = [], [], []
+    for j in range(len(stop)):
+        l, f, b = int(lb[j]), int(fwd[j]), int(back[j])
+        fs, bs = int(stop[j]) & 15, int(stop[j]) >> 4
+        ftrim = fs in far and bool(trims[l + f])
+        btrim = bs in far and bool(trims[l - b - 1])
+        if (f + b == 0 and fs in (KAD_SR_STOP_END, KAD_SR_STOP_FAR) and bs in (KAD_SR_STOP_END, KAD_SR_STOP_FAR)
+                and not ftrim and not btrim):
+            skipped.append(j)
+            continue
+        lo = l - b - (0 if bs == KAD_SR_STOP_END else 1)
+        hi = l + f - (1 if fs == KAD_SR_STOP_END else 0)
+        if lo <= hi and not marked[lo:hi + 1].any() and hi < block_up and lo > block_down:
+            pairs = [(s, 1) for s in range(l, l + f)] + [(s, 1) for s in range(l - 1, l - b - 1, -1)]
+            if ftrim:
+                pairs.append((l + f, 0))
+            if btrim:
+                pairs.append((l - b - 1, 0))
+            ready.append((j, pairs))
+        else:
+            deferred.append(j)
+            if lo <= hi:
+                if fs in open_stops:
+                    block_up = min(block_up, lo)
+                if bs in open_stops:
+                    block_down = max(block_down, hi)
+        if lo <= hi:
+            marked[lo:hi + 1] = True
+    return skipped, ready, deferred
+
+
+def _host_states(host, idx, now):
+    flags, off, nid, nfl = [], [0], [np.zeros((0, 20), np.uint8)], [np.zeros(0, np.uint8)]
+    for s in idx:
+        fl, ids_s, nf_s = host.state(int(s), now)
+        flags.append(fl)
+        if len(ids_s):
+            nid.append(_as_ids(ids_s))
+            nfl.append(np.asarray(nf_s, dtype=np.uint8).reshape(-1))
+        off.append(off[-1] + len(ids_s))
+    return np.array(flags, np.uint8), np.array(off, np.uint32), np.concatenate(nid), np.concatenate(nfl)
+
+
+def _patch_from_host(DS, host, idx, now) -> None:
+    """The searches idx (any order, repeats allowed) from the host's lists; the slabs grow when a list no longer fits."""
+    idx = sorted(set(int(s) for s in idx))
+    if not idx:
+        return
+    flags, off, nid, nfl = _host_states(host, idx, now)
+    longest = int(np.diff(off).max())
+    if longest > DS.cap:
+        DS.grow(max(longest, 2 * DS.cap))
+    DS.patch(np.array(idx, np.uint32), flags, off, nid, nfl)
+
+
+def _host_walk(host, S: int, l: int, j: int, touched: list) -> bool:
+    """Dht::trySearchInsert's two walks of candidate j from its lower bound l on the host; the probed searches are
+    appended to touched. True if any search accepted."""
+    inserted = False
+    s = l
+    while s < S:  # insert forward (dht.cpp:826-836)
+        touched.append(s)
+        if not host.insert(s, j):
+            break
+        inserted = True
+        s += 1
+    s = l
+    while s > 0:  # insert backward (dht.cpp:837-847)
+        s -= 1
+        touched.append(s)
+        if not host.insert(s, j):
+            break
+        inserted = True
+    return inserted
+
+
+def try_search_insert_device(DS, host, cand_ids, now, max_rounds=8) -> dict:
+    """Dht::trySearchInsert for the candidates cand_ids ((q, 20) uint8, in arrival order) over the searches of DS,
+    with the accepted inserts applied on the device: rounds of one verdict launch for the remaining
+    candidates, plan_insert_round, one DS.insert of the ready pairs and the host's replay of the ready candidates
+    (host.insert(s, j) forwards, then backwards, until the first refusal; any result that differs from the device's
+    byte or from the verdict raises). Deferred candidates wait for the next round; after max_rounds rounds (None: no
+    limit) the rest takes the reference walk on the host, in order, followed by one patch. Searches the device
+    reports as KAD_SR_INSERT_OVERFLOW are patched from the host's lists, the slabs grown when a list no longer fits.
+
+    `host` holds the real searches: insert(s, j) -> bool, state(s, now) -> (flags, node_ids, node_flags) with
+    KAD_SN_REMOVABLE evaluated at `now`, bad(j) -> node->isExpired() of candidate j, old(j) -> its node is removable at
+    `now` (expired and time + NODE_EXPIRE_TIME < now), holders(j) -> the searches that hold its node. The device set's
+    KAD_SN_REMOVABLE bits must be those of `now` (as for refill_searches). A candidate that is old is a barrier:
+    old(j) is asked when the scan reaches j, after every earlier old candidate has been applied; everything before it
+    is finished by rounds, then it takes the host walk, and the searches it probed are patched together with, if any
+    search accepted it, every search of holders(j) (node.time = now clears its REMOVABLE bit wherever it is a member).
+
+    Returns {"skipped", "device", "host", "rounds", "pairs", "overflowed"}."""
+    cand = _as_ids(cand_ids)
+    q = cand.shape[0]
+    counts = {"skipped": 0, "device": 0, "host": 0, "rounds": 0, "pairs": 0, "overflowed": 0}
+
+    def rounds(rem):
+        """Rounds over the candidates rem (ascending positions) until none is left or the budget is spent: what is left."""
+        # kad_sr_insert holds a list in one wave: slabs grown past 64 entries leave the rest to the host path
+        while rem and DS.cap <= 64 and (max_rounds is None or counts["rounds"] < max_rounds):
+            counts["rounds"] += 1
+            ids = cand[rem]
+            lb, fwd, back, stop = DS.try_insert_host(ids)
+            st = DS.export(nodes=False)
+            trims = (st["full"] != 0) & (st["t"] < st["n"])
+            skipped, ready, deferred = plan_insert_round(DS.S, lb, fwd, back, stop, trims)
+            counts["skipped"] += len(skipped)
+            counts["device"] += len(ready)
+            pairs = sorted((s, rem[k], want) for k, pr in ready for s, want in pr)  # one candidate per search
+            got, over = {}, set()
+            if pairs:
+                which = np.array([p[0] for p in pairs], np.uint32)
+                js = [p[1] for p in pairs]
+                ins, status = DS.insert(which, np.arange(len(pairs) + 1, dtype=np.uint32), cand[js],
+                                        np.array([KAD_SN_BAD if host.bad(j) else 0 for j in js], np.uint8))
+                counts["pairs"] += len(pairs)
+                over = set(int(s) for s in which[status == KAD_SR_INSERT_OVERFLOW])
+                got = {(p[0], p[1]): (int(ins[k]), p[2]) for k, p in enumerate(pairs)}
+            for k, _ in ready:  # the replay: the reference's own walk, checked against the device and the verdict
+                j, l, f, b = rem[k], int(lb[k]), int(fwd[k]), int(back[k])
+                for rng, end in ((range(l, DS.S), l + f), (range(l - 1, -1, -1), l - b - 1)):
+                    for s in rng:
+                        r = bool(host.insert(s, j))
+                        if r != (s != end):
+                            raise RuntimeError(f"try_search_insert_device: search {s} answered {r} to candidate {j} "
+                                               "against its verdict")
+                        if (s, j) in got and s not in over and got[(s, j)][0] != int(r):
+                            raise RuntimeError(f"try_search_insert_device: search {s}, candidate {j}: the host "
+                                               f"answered {r}, the device {got[(s, j)][0]}")
+                        if not r:
+                            break
+            if over:
+                counts["overflowed"] += len(over)
+                _patch_from_host(DS, host, over, now)
+            rem = [rem[k] for k in deferred]
+        return rem
+
+    dirty, pos = [], 0
+    left = []  # what the rounds left when the budget ran out, and everything after it: the host path, in order
+    while pos < q:
+        end = pos
+        while end < q and not (host.bad(end) and host.old(end)):
+            end += 1
+        segment = list(range(pos, end))
+        left = left + segment if left else rounds(segment)
+        if end < q:  # the barrier
+            if left:  # the budget is spent: the old candidate waits its turn on the host path
+                left.append(end)
+            else:
+                counts["host"] += 1
+                touched = []
+                lb = DS.try_insert_host(cand[end:end + 1])[0]
+                if _host_walk(host, DS.S, int(lb[0]), end, touched):
+                    touched += [int(s) for s in host.holders(end)]
+                _patch_from_host(DS, host, touched, now)
+        pos = end + 1
+    if left:
+        lbs = DS.try_insert_host(cand[left])[0]
+        for k, j in enumerate(left):
+            counts["host"] += 1
+            was_old = bool(host.bad(j) and host.old(j))
+            holders = [int(s) for s in host.holders(j)] if was_old else []
+            if _host_walk(host, DS.S, int(lbs[k]), j, dirty):
+                dirty += holders
+        _patch_from_host(DS, host, dirty, now)
     return counts
 
 
