@@ -625,6 +625,52 @@ int kad_sr_insert(kad_searches* ss, uint32_t m, const uint32_t* which, const uin
  * last kad_sr_insert on this set, in milliseconds (0 before the first). */
 int kad_sr_insert_kernel_ms(const kad_searches* ss, float* out_ms);
 
+/* ---- Node status changes over a set of live searches (SearchNode::isBad dht.cpp:458-460, Node::setExpired) ---- */
+/* The reference keeps no flag byte: isBad() reads the shared Node, so one setExpired() after a timed-out request, one
+ * reply (expired_ = false) or ten minutes passing for an expired node changes KAD_SN_BAD / KAD_SN_REMOVABLE in every
+ * search that holds the node. kad_sr_mark_nodes carries such changes to the device set without the host knowing the
+ * holders and without an upload of their lists. Node identity is the 20-byte ID.
+ *   node ops   for every search s and every entry e < n of its list whose ID equals node_ids[j], the flag byte becomes
+ *              (f & ~clear_bits[j]) | set_bits[j].
+ *   pairs      then, for every pair k whose search pair_which[k] holds pair_ids[k], the flag byte becomes exactly
+ *              pair_flags[k] (the per-search `candidate` bit, dht.cpp:1038, 1109, which no node op can express). A pair
+ *              that is not found changes nothing and reports 0.
+ *   fix-up     every search with at least one flag byte that differs from before the call is changed: its record is
+ *              rewritten to what kad_searches_create derives from the same list with the new flag bytes. n, the order,
+ *              the IDs and KAD_SR_EXPIRED are untouched; only t, full and the threshold can move. Nothing is trimmed,
+ *              popped or erased (the reference does that on the next insertNode). An expired search's record does not
+ *              depend on the flag bytes; it is still reported as changed. A search that is hit but whose bytes all stay
+ *              equal is counted in out_hits, is not in out_changed, and none of its device bytes is written.
+ * out_hits[j]: the searches whose list holds node j. out_pair_found[k]: 1 if the pair was found. out_changed[0 ..
+ * *out_n_changed): the changed searches, ascending; room for S indices. out_counts[4k ..] belongs to out_changed[k]: n,
+ * Search::getNumberOfBadNodes(), getNumberOfConsecutiveBadNodes() (dht.cpp:583-597) and the record's bits (1 = full,
+ * 2 = expired); room for S x 4 bytes. From these the host reads searchStep's expiry test, lead_bad >= min(n,
+ * SEARCH_MAX_BAD_NODES) (:1451), and the refill test, n - bad < SEARCH_NODES (:1354), without touching its lists; the
+ * search-level expire() itself stays with kad_searches_patch / kad_searches_apply. Padding slots at or past n never
+ * match, whatever the batch holds.
+ * Host arrays, synchronous; it first waits for all device work enqueued before the call, uploads its arguments as one
+ * copy and reads its outputs back as one (a second one only when more than 2q + p + 64 searches changed). node_ids:
+ * q x 20 B, any order, distinct. clear_bits / set_bits: q bytes each, NULL = all zero. Checked in this order, before
+ * any device work, every failure leaving the set unchanged: NULL ss, out_changed or out_n_changed; NULL node_ids with
+ * q > 0; NULL pair_which / pair_ids / pair_flags with p > 0; a bit other than KAD_SN_BAD | KAD_SN_REMOVABLE in
+ * clear_bits, set_bits or pair_flags; clear_bits[j] & set_bits[j] != 0; two equal node IDs; pair_which[k] >= S; two
+ * equal (search, ID) pairs (all KAD_ERR_INVALID); q > KAD_SR_MARK_MAX_NODES; cap > 64 (both KAD_ERR_UNSUPPORTED);
+ * q == 0 and p == 0, or S == 0 (KAD_OK, *out_n_changed = 0, hits and found zeroed). Equal node IDs are found by sorting,
+ * so the limit on q answers only after the batch was sorted: a q beyond what the host can allocate for that (about 30
+ * bytes per node) answers KAD_ERR_NOMEM instead of KAD_ERR_UNSUPPORTED. The dirty bitmap and the changed
+ * list are scratch of the handle, allocated by the first call that reaches the device and counted in
+ * kad_searches_info's device_bytes from then on. */
+#define KAD_SR_MARK_MAX_NODES (1u << 20)
+int kad_sr_mark_nodes(kad_searches* ss,
+                      uint32_t q, const uint8_t* node_ids,
+                      const uint8_t* clear_bits, const uint8_t* set_bits,
+                      uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids, const uint8_t* pair_flags,
+                      uint32_t* out_hits, uint8_t* out_pair_found, uint32_t* out_changed, uint8_t* out_counts,
+                      uint32_t* out_n_changed);
+/* Measurement aid (tools/sr_mark_bench.py), as kad_sr_insert_kernel_ms: the device times of the scan kernel and of the
+ * fix kernel of the last kad_sr_mark_nodes on this set, in milliseconds (0 before the first). */
+int kad_sr_mark_kernel_ms(const kad_searches* ss, float* out_scan_ms, float* out_fix_ms);
+
 /* Per-query family select for NodeCache::getCachedNodes(id, sa_family, count) (node_cache.cpp:36-66:
  * cache_4 or cache_6 by family; Dht::refill asks the search's family, dht.cpp:1650): af[i] = 0 -> table4,
  * 1 -> table6 (KAD_TABLE_SORTED tables; either may be NULL = an empty map). Any count (as kad_nc_closest_batch).

@@ -32,6 +32,7 @@
 #include <sys/socket.h>  // AF_INET (sa_family_t), as OpenDHT's sockaddr.h
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <climits>
 #include <cstdint>
@@ -837,6 +838,17 @@ struct InsertResult {
     bool overflow;
 };
 
+/* One search whose flag bytes SearchesMirror::markNodes changed, with the counts of its list after the change: n,
+ * Search::getNumberOfBadNodes(), getNumberOfConsecutiveBadNodes() (dht.cpp:583-597), and whether it is full (at least
+ * SEARCH_NODES entries that are not bad) and expired. Dht::searchStep's expiry test is lead_bad >= min(n,
+ * SEARCH_MAX_BAD_NODES) (:1451), its refill test n - bad < SEARCH_NODES (:1354). */
+template <class InfoHashT>
+struct MarkedSearch {
+    InfoHashT id;
+    uint8_t n, bad, lead_bad;
+    bool full, expired;
+};
+
 /* Device mirror of one family's live searches (Dht::searches(af), dht.h) over a map shaped like
  * std::map<InfoHash, std::shared_ptr<Search>>. Reads of a search: id, expired, nodes[i].node->id, nodes[i].isBad().
  * The map must outlive the mirror or the next snapshot. */
@@ -922,7 +934,11 @@ public:
      * Precondition: which bits "differ" is worked out from each member node's current isExpired() and time against
      * the time the search was last uploaded at, so every change of those two fields of a node held by a mirrored
      * search (setExpired, a reply, another search's insertNode writing node->time) must have been reported through
-     * sync(changed, now) before; a search whose members changed unreported may keep stale bits on the device. */
+     * markNodes(nodes, pairs, now) before (or, for a search whose list changed as well, through sync(changed, now)); a
+     * search whose members changed unreported may keep stale bits on the device. markNodes leaves the upload times
+     * alone: for fixed node fields removability only ever turns on as time passes, so the bit markNodes wrote at T1 lies
+     * between what an upload at the recorded time <= T1 would hold and what `now` >= T1 asks for; whenever those two
+     * agree the device bit agrees with them, and when they do not the search is patched, as before. */
     template <class NodeMapT, class InfoHashT, class TimePoint>
     std::vector<RefillResult<typename NodeCacheFamilyMirror<NodeMapT>::NodePtr>>
     refillBatch(const NodeCacheFamilyMirror<NodeMapT>& nc, const std::vector<InfoHashT>& ids, TimePoint now) {
@@ -1056,6 +1072,84 @@ public:
             r.overflow = st[k] != KAD_SR_INSERT_OK;
             if (!r.overflow) r.inserted.assign(ins.begin() + off[k], ins.begin() + off[k + 1]);
             at_[which[k]] = when.ns();
+        }
+        return out;
+    }
+
+    /* Node status changes of one tick carried to every mirrored search that holds the node, without the host looking
+     * for the holders and without an upload of their lists: one kad_sr_mark_nodes. nodes: the Nodes whose isExpired()
+     * or time changed since they were last reported (setExpired after a timed-out request, a reply, an expired node
+     * whose ten minutes ran out), in any order, repeats allowed: an expired node gets KAD_SN_BAD and, at `now`,
+     * KAD_SN_REMOVABLE or not; a live one loses both. pairs: (search ID, node) for every list entry whose `candidate`
+     * changed (dht.cpp:1038, 1109), and for every entry with `candidate` set whose node is in `nodes` (its BAD bit is
+     * not the node's): the entry gets exactly the byte the host's list says, isBad() and removability at `now`. A pair
+     * whose search does not hold the node changes nothing. The lists themselves must be the mirrored ones (insertNode,
+     * trims and erases go through insertBatch, refillBatch or sync). Returns the searches with a byte that changed, in
+     * map order, with their counts; the search-level expire() stays with sync / update. A mirror of no searches takes
+     * any `nodes` and returns nothing; a pair always names a mirrored search (KAD_ERR_INVALID otherwise). */
+    template <class NodePtrT, class InfoHashT, class TimePoint>
+    std::vector<MarkedSearch<InfoHashT>> markNodes(const std::vector<NodePtrT>& nodes,
+                                                   const std::vector<std::pair<InfoHashT, NodePtrT>>& pairs,
+                                                   TimePoint now) {
+        std::vector<MarkedSearch<InfoHashT>> out;
+        if (nodes.empty() && pairs.empty()) return out;
+        if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::markNodes before snapshot");
+        if (size() == 0 && pairs.empty()) return out;  // a family without live searches: no list holds the nodes
+        const At<TimePoint> when{now};
+        const uint8_t both = KAD_SN_BAD | KAD_SN_REMOVABLE;
+        // one op per node ID: (ID, set bits), sorted, repeats dropped
+        std::vector<std::array<uint8_t, KAD_HASH_LEN + 1>> ops(nodes.size());
+        for (size_t j = 0; j < nodes.size(); j++) {
+            std::memcpy(ops[j].data(), id_bytes(nodes[j]->id), KAD_HASH_LEN);
+            ops[j][KAD_HASH_LEN] = !nodes[j]->isExpired() ? (uint8_t)0
+                                   : when.removable(*nodes[j]) ? both : (uint8_t)KAD_SN_BAD;
+        }
+        std::sort(ops.begin(), ops.end());
+        ops.erase(std::unique(ops.begin(), ops.end()), ops.end());
+        std::vector<uint8_t> nid, clr, set;
+        for (const auto& o : ops) {
+            nid.insert(nid.end(), o.begin(), o.begin() + KAD_HASH_LEN);
+            set.push_back(o[KAD_HASH_LEN]);
+            clr.push_back((uint8_t)(both & ~o[KAD_HASH_LEN]));
+        }
+        // one override per (search, node ID): the byte of the host's own entry
+        std::vector<std::pair<uint32_t, std::array<uint8_t, KAD_HASH_LEN + 1>>> pr(pairs.size());
+        for (size_t k = 0; k < pairs.size(); k++) {
+            pr[k].first = index_of(id_bytes(pairs[k].first));
+            const auto& n = pairs[k].second;
+            std::memcpy(pr[k].second.data(), id_bytes(n->id), KAD_HASH_LEN);
+            bool bad = n->isExpired();
+            const auto it = map_->find(pairs[k].first);
+            if (it == map_->end()) throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
+            for (const auto& sn : it->second->nodes)
+                if (std::memcmp(id_bytes(sn.node->id), id_bytes(n->id), KAD_HASH_LEN) == 0) bad = sn.isBad();
+            pr[k].second[KAD_HASH_LEN] = (uint8_t)((bad ? KAD_SN_BAD : 0u) | (when.removable(*n) ? KAD_SN_REMOVABLE : 0u));
+        }
+        std::sort(pr.begin(), pr.end());
+        pr.erase(std::unique(pr.begin(), pr.end()), pr.end());
+        std::vector<uint32_t> pw;
+        std::vector<uint8_t> pid, pfl;
+        for (const auto& e : pr) {
+            pw.push_back(e.first);
+            pid.insert(pid.end(), e.second.begin(), e.second.begin() + KAD_HASH_LEN);
+            pfl.push_back(e.second[KAD_HASH_LEN]);
+        }
+        std::vector<uint32_t> changed(size());
+        std::vector<uint8_t> counts(4 * size());
+        uint32_t n_changed = 0;
+        check(kad_sr_mark_nodes(ss_, (uint32_t)set.size(), nid.data(), clr.data(), set.data(), (uint32_t)pw.size(),
+                                pw.data(), pid.data(), pfl.data(), nullptr, nullptr, changed.data(), counts.data(),
+                                &n_changed), "kad_sr_mark_nodes");
+        out.resize(n_changed);
+        auto it = map_->begin();
+        uint32_t at = 0;
+        for (uint32_t k = 0; k < n_changed; k++) {
+            std::advance(it, changed[k] - at);
+            at = changed[k];
+            if (it == map_->end() || std::memcmp(id_bytes(it->first), &ids_[(size_t)at * KAD_HASH_LEN], KAD_HASH_LEN) != 0)
+                throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
+            out[k] = MarkedSearch<InfoHashT>{it->first, counts[4 * k], counts[4 * k + 1], counts[4 * k + 2],
+                                            (counts[4 * k + 3] & 1) != 0, (counts[4 * k + 3] & 2) != 0};
         }
         return out;
     }
@@ -1305,6 +1399,13 @@ public:
     std::vector<InsertResult> insertBatch(sa_family_t af, const std::vector<InfoHashT>& ids,
                                           const std::vector<std::vector<NodePtrT>>& nodes) {
         return searches(af).insertBatch(ids, nodes, clock_());
+    }
+    /* The node status changes of one tick for the searches of one family, at the mirror's clock
+     * (SearchesMirror::markNodes). */
+    template <class NodePtrT, class InfoHashT>
+    std::vector<MarkedSearch<InfoHashT>> markNodes(sa_family_t af, const std::vector<NodePtrT>& nodes,
+                                                   const std::vector<std::pair<InfoHashT, NodePtrT>>& pairs) {
+        return searches(af).markNodes(nodes, pairs, clock_());
     }
     template <class InfoHashT>
     void syncSearches(sa_family_t af, const std::vector<InfoHashT>& changed, time_point now) {

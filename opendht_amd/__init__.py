@@ -15,10 +15,11 @@ from ._lib import (KAD_SN_BAD, KAD_SR_EXPIRED, KAD_SR_STOP_END, KAD_SR_STOP_FAR,
                    KAD_SR_STOP_KNOWN)
 from ._lib import KAD_SN_REMOVABLE, KAD_SR_REFILL_OK, KAD_SR_REFILL_OVERFLOW
 from ._lib import KAD_SR_INSERT_OK, KAD_SR_INSERT_OVERFLOW
+from ._lib import KAD_SR_MARK_MAX_NODES
 from ._lib import KAD_SWEEP_INCOMING
 from .ingest import ingest
-from .searches import (DeviceSearches, expire_searches, plan_insert_round, refill_searches, start_searches,
-                       try_search_insert, try_search_insert_device)
+from .searches import (DeviceSearches, expire_searches, mark_search_nodes, plan_insert_round, refill_searches,
+                       start_searches, try_search_insert, try_search_insert_device)
 from .table import DeviceTable, nc_closest_dual, rt_closest_dual, rt_responsible_dual
 
 __all__ = [
@@ -32,4 +33,5 @@ __all__ = [
     "KAD_SN_REMOVABLE", "KAD_SR_REFILL_OK", "KAD_SR_REFILL_OVERFLOW", "refill_searches",
     "start_searches", "expire_searches",
     "KAD_SR_INSERT_OK", "KAD_SR_INSERT_OVERFLOW", "plan_insert_round", "try_search_insert_device",
+    "KAD_SR_MARK_MAX_NODES", "mark_search_nodes",
 ]

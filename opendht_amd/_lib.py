@@ -42,6 +42,7 @@ KAD_SR_EXPIRED, KAD_SN_BAD = 0x01, 0x01
 KAD_SN_REMOVABLE = 0x02
 KAD_SR_REFILL_OK, KAD_SR_REFILL_OVERFLOW = 0, 1
 KAD_SR_INSERT_OK, KAD_SR_INSERT_OVERFLOW = 0, 1
+KAD_SR_MARK_MAX_NODES = 1 << 20
 KAD_SR_STOP_END, KAD_SR_STOP_KNOWN, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED = 0, 1, 2, 3
 KAD_SWEEP_INCOMING = 1
 
@@ -157,6 +158,8 @@ SIGNATURES = {
     "kad_sr_refill_kernel_ms": (C.c_int, [_P, _P]),
     "kad_sr_insert": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "kad_sr_insert_kernel_ms": (C.c_int, [_P, _P]),
+    "kad_sr_mark_nodes": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "kad_sr_mark_kernel_ms": (C.c_int, [_P, _P, _P]),
     "kad_rt_shard_batch": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
                                      _P, _P]),

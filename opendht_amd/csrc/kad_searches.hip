@@ -25,12 +25,18 @@
 // each with its own KAD_SN_BAD bit, applied in place by insert_kernel in the same one-wave-per-search form: the accepted
 // inserts of a trySearchInsert tick without an upload of the touched lists.
 //
+// kad_sr_mark_nodes carries node status changes (Node::setExpired, a reply, the candidate bit) to the
+// flag bytes of every list that holds the node: mark_scan_kernel streams the member keys against the tick's sorted batch
+// of node IDs, mark_pairs_kernel sets single (search, node) entries, mark_fix_kernel derives the changed searches'
+// records again.
+//
 // kad_searches_apply changes the membership (Dht::search dht.cpp:1673-1735, Dht::expireSearches
 // :1060-1074) and the slab size: the host plans one source word per new search, searches_relayout_kernel gathers the
 // records and slabs into new arrays beside the old ones, searches_rdx_kernel rebuilds the prefix directory, and the
 // handle's arrays are swapped once everything succeeded.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <new>
@@ -44,7 +50,8 @@
 
 // tests/test_refill_abi.py, test_searches_abi.py and test_searches_apply_abi.py hand the argument checks a zeroed
 // buffer for a set: it must read as a set of no searches (S == 0, cap == 0, no pointer followed before the checks end,
-// rf_ms == 0); tests/test_sr_insert_abi.py does the same (in_ms == 0).
+// rf_ms == 0); tests/test_sr_insert_abi.py does the same (in_ms == 0), and tests/test_sr_mark_abi.py (no mark scratch,
+// mk_ms == 0).
 struct kad_searches {
     int device = 0;
     uint32_t S = 0, cap = 0;
@@ -61,6 +68,13 @@ struct kad_searches {
     float rf_ms = 0.f;
     hipEvent_t in_ev[2] = {nullptr, nullptr};  // around the last kad_sr_insert's insert kernel
     float in_ms = 0.f;
+    // kad_sr_mark_nodes' scratch, allocated by the first call and again when the set outgrew it: the count of changed
+    // searches, their (search, count word) pairs, the dirty bitmap and the changed list, for mk_cap searches
+    uint8_t* mk_buf = nullptr;
+    uint32_t mk_cap = 0;
+    uint64_t mk_bytes = 0;
+    hipEvent_t mk_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the last call's scan and fix kernels
+    float mk_ms[2] = {0.f, 0.f};
 };
 
 namespace {
@@ -648,6 +662,217 @@ __global__ __launch_bounds__(BLOCK) void insert_kernel(DevInsert D) {
     if (lane == 0) D.out_status[i] = overflow ? (uint8_t)KAD_SR_INSERT_OVERFLOW : (uint8_t)KAD_SR_INSERT_OK;
 }
 
+// ---- kad_sr_mark_nodes: node status changes over the set -----------------------------------------
+// A node's isExpired() or time changed: every list that holds it carries a stale flag byte. mark_scan_kernel streams
+// the S x cap member keys once, one entry per lane, against the sorted batch of changed IDs; mark_pairs_kernel sets the
+// exact byte of single (search, node) pairs (the per-search `candidate` bit); mark_fix_kernel derives the records of the
+// searches whose bytes changed again. An entry that a pair names belongs to the pair alone: the scan counts its hit and
+// leaves the byte to mark_pairs_kernel, so every byte is written at most once, by one lane, and "changed" compares the
+// byte before the call with the one after it.
+constexpr uint32_t MARK_LDS_KEYS = kadplan::SR_MARK_SMALL_BATCH;  // 32 KB of batch keys per workgroup, and next to
+constexpr uint32_t MARK_LDS_DIR = (1u << kadplan::SR_MARK_DIR_BITS_SMALL) + 1;  // them 4 KB of directory; larger batches
+constexpr uint32_t MARK_UNROLL = 4;  // are read through L2. Member keys in flight per lane.
+constexpr uint32_t MARK_FIX_GRID = 1024;  // wave-stride beyond
+constexpr uint32_t MARK_HEAD_BYTES = 16;
+
+struct DevMark {
+    uint32_t* rec;
+    const uint64_t* mkey;
+    const uint32_t* mtail;
+    uint8_t* mflag;
+    uint32_t S, cap, total;  // total = S x cap < 2^31
+    uint32_t q;              // the batch, ascending by (key, tail)
+    const uint64_t* bkey;
+    const uint32_t* btail;
+    const uint8_t* bop;      // clear | set << 2
+    const uint32_t* dir;     // 2^B + 1 words: the lower bound of every B-bit key prefix among the batch keys
+    uint32_t dshift;         // 64 - B
+    uint32_t p;              // the pairs, ascending by (search, ID)
+    const uint32_t* pw;
+    const uint64_t* pkey;
+    const uint32_t* ptail;
+    const uint8_t* pfl;
+    uint32_t* hits;          // q, by batch position; NULL when the caller does not ask for them
+    uint8_t* found;          // p, by pair position
+    uint32_t* head;          // the number of changed searches
+    uint32_t* bitmap;        // one bit per search: some byte of it changed
+    uint32_t* list;          // the changed searches in the order they were first marked
+};
+
+// search s changed: the lane that flips its bit appends it to the list
+__device__ __forceinline__ void mark_dirty(const DevMark& D, uint32_t s) {
+    const uint32_t bit = 1u << (s & 31u);
+    if (!(atomicOr(D.bitmap + (s >> 5), bit) & bit)) D.list[atomicAdd(D.head, 1u)] = s;
+}
+
+// a pair names entry (k, t0..t2) of search s
+__device__ __forceinline__ bool pair_owns(const DevMark& D, uint32_t s, uint64_t k, uint32_t t0, uint32_t t1,
+                                          uint32_t t2) {
+    uint32_t lo = 0, hi = D.p;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (D.pw[mid] < s)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    for (; lo < D.p && D.pw[lo] == s; lo++) {
+        const uint32_t* tl = D.ptail + 3ull * lo;
+        if (D.pkey[lo] == k && tl[0] == t0 && tl[1] == t1 && tl[2] == t2) return true;
+    }
+    return false;
+}
+
+// member entry i with key k against the batch: sk / sd are the staged keys and directory of the LDS form
+template <bool LDS>
+__device__ __forceinline__ void mark_one(const DevMark& D, const uint64_t* sk, const uint16_t* sd, uint32_t i, uint64_t k) {
+    // the batch keys of the member key's prefix, then the lower bound among them: for keys spread like hashes a
+    // bucket holds one key or none, so the common lane reads two directory words and at most one key
+    const uint32_t p = (uint32_t)(k >> D.dshift);
+    uint32_t lo = LDS ? (uint32_t)sd[p] : D.dir[p];
+    const uint32_t end = LDS ? (uint32_t)sd[p + 1] : D.dir[p + 1];
+    uint32_t hi = end;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if ((LDS ? sk[mid] : D.bkey[mid]) < k)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    if (lo >= end || (LDS ? sk[lo] : D.bkey[lo]) != k) return;  // the common lane: 8 bytes of HBM, nothing else
+    // a key hit: the run of equal keys against the member's tail, then the index against n (a zero key of the
+    // batch meets the padding of every slab here)
+    const uint32_t* tl = D.mtail + 3ull * i;
+    const uint32_t t0 = tl[0], t1 = tl[1], t2 = tl[2];
+    for (uint32_t j = lo; j < D.q && (LDS ? sk[j] : D.bkey[j]) == k; j++) {
+        const uint32_t* bt = D.btail + 3ull * j;
+        if (bt[0] != t0 || bt[1] != t1 || bt[2] != t2) continue;
+        const uint32_t s = i / D.cap, e = i - s * D.cap;
+        if (e < min(D.rec[(uint64_t)SREC_WORDS * s + SREC_N], D.cap)) {
+            if (D.hits) atomicAdd(D.hits + j, 1u);
+            if (!(D.p && pair_owns(D, s, k, t0, t1, t2))) {
+                const uint32_t f = D.mflag[i], op = D.bop[j], nf = (f & ~(op & 3u)) | (op >> 2);
+                if (nf != f) {
+                    D.mflag[i] = (uint8_t)nf;
+                    mark_dirty(D, s);
+                }
+            }
+        }
+        break;  // the batch IDs are distinct
+    }
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(BLOCK) void mark_scan_kernel(DevMark D) {
+    __shared__ uint64_t sk[LDS ? MARK_LDS_KEYS : 1];
+    __shared__ uint16_t sd[LDS ? MARK_LDS_DIR + 1 : 2];  // a batch of up to 4096 keys: its bounds fit 16 bits
+    if (LDS) {
+        for (uint32_t j = threadIdx.x; j < D.q; j += BLOCK) sk[j] = D.bkey[j];
+        for (uint32_t j = threadIdx.x; j <= (1u << (64u - D.dshift)); j += BLOCK) sd[j] = (uint16_t)D.dir[j];
+        __syncthreads();
+    }
+    const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i0 < D.total; i0 += MARK_UNROLL * stride) {
+        uint64_t k[MARK_UNROLL];  // all loads of the step in flight together, none predicated
+#pragma unroll
+        for (uint32_t u = 0; u < MARK_UNROLL; u++) {
+            const uint64_t iu = i0 + u * stride;
+            k[u] = __builtin_nontemporal_load(D.mkey + (iu < D.total ? iu : (uint64_t)D.total - 1u));
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < MARK_UNROLL; u++) {
+            const uint64_t iu = i0 + u * stride;
+            if (iu < D.total) mark_one<LDS>(D, sk, sd, (uint32_t)iu, k[u]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void mark_pairs_kernel(DevMark D) {
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= D.p) return;
+    const uint32_t s = D.pw[k], n = min(D.rec[(uint64_t)SREC_WORDS * s + SREC_N], D.cap);
+    const uint64_t x = D.pkey[k];
+    const uint32_t* xt = D.ptail + 3ull * k;
+    const uint32_t x0 = xt[0], x1 = xt[1], x2 = xt[2];
+    const uint64_t* mk = D.mkey + (uint64_t)s * D.cap;
+    const uint32_t* mt = D.mtail + 3ull * s * D.cap;
+    uint32_t at = n;
+    // member()'s walk: keys eight at a time, none predicated, a tail only on a key hit
+    for (uint32_t c = 0; c < n && at == n; c += 8) {
+        uint64_t v[8];
+#pragma unroll
+        for (uint32_t u = 0; u < 8; u++) v[u] = mk[min(c + u, n - 1u)];
+#pragma unroll
+        for (uint32_t u = 0; u < 8; u++) {
+            if (at == n && c + u < n && v[u] == x) {
+                const uint32_t* tl = mt + 3ull * (c + u);
+                if (tl[0] == x0 && tl[1] == x1 && tl[2] == x2) at = c + u;
+            }
+        }
+    }
+    D.found[k] = at < n ? (uint8_t)1 : (uint8_t)0;
+    if (at < n) {
+        uint8_t* f = D.mflag + (uint64_t)s * D.cap + at;
+        const uint8_t want = D.pfl[k];
+        if (*f != want) {
+            *f = want;
+            mark_dirty(D, s);
+        }
+    }
+}
+
+// One wave per changed search, one entry per lane: t, SREC_FULL and the threshold from the new flag bytes as
+// refill_kernel's tail writes them, and the count word n | bad << 8 | lead_bad << 16 | bits << 24. res[w] (w < n_res)
+// pairs the search with its count word in the call's own buffer, which travels back with the other outputs; all[w] is
+// the same pair in the handle's scratch, for a call that changed more searches than that.
+__global__ __launch_bounds__(BLOCK) void mark_fix_kernel(DevMark D, uint64_t* __restrict__ all,
+                                                         uint32_t* __restrict__ out_head, uint64_t* __restrict__ res,
+                                                         uint32_t n_res) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = rfl(blockIdx.x * REFILL_WAVES + (threadIdx.x >> 6)), waves = gridDim.x * REFILL_WAVES;
+    const uint32_t n_changed = min(rfl(D.head[0]), D.S);
+    if (wave == 0 && lane == 0) *out_head = n_changed;
+    for (uint32_t w = wave; w < n_changed; w += waves) {
+        const uint32_t s = min(rfl(D.list[w]), D.S - 1u);
+        uint32_t* r = D.rec + (uint64_t)SREC_WORDS * s;
+        const uint32_t n = min(rfl(r[SREC_N]), D.cap);
+        const bool expired = (rfl(r[SREC_BITS]) & SREC_EXPIRED) != 0;
+        const uint64_t e0 = (uint64_t)s * D.cap + lane;
+        const bool in = lane < n;
+        const uint32_t fl = in ? D.mflag[e0] : 0u;
+        const uint64_t badm = __ballot(in && (fl & KAD_SN_BAD)), goodm = __ballot(in && !(fl & KAD_SN_BAD));
+        bool full;
+        uint32_t t;
+        wave_trim(expired, n, goodm, lane, full, t);
+        if (lane + 1u == t || (t == 0 && lane == 0)) {  // the threshold entry[t-1], zero for t == 0
+            uint64_t k = 0;
+            uint32_t t0 = 0, t1 = 0, t2 = 0;
+            if (t) {
+                k = D.mkey[e0];
+                const uint32_t* tl = D.mtail + 3ull * e0;
+                t0 = tl[0];
+                t1 = tl[1];
+                t2 = tl[2];
+            }
+            r[SREC_THR] = (uint32_t)k;
+            r[SREC_THR + 1] = (uint32_t)(k >> 32);
+            r[SREC_THR + 2] = t0;
+            r[SREC_THR + 3] = t1;
+            r[SREC_THR + 4] = t2;
+        }
+        if (lane == 0) {
+            const uint32_t bits = (full ? SREC_FULL : 0u) | (expired ? SREC_EXPIRED : 0u);
+            const uint32_t bad = (uint32_t)__popcll(badm);
+            const uint32_t lead = min(~badm ? (uint32_t)__builtin_ctzll(~badm) : 64u, n);
+            const uint32_t cw = n | (bad << 8) | (lead << 16) | (bits << 24);
+            r[SREC_T] = t;
+            r[SREC_BITS] = bits;
+            all[w] = ((uint64_t)cw << 32) | s;
+            if (w < n_res) res[w] = ((uint64_t)cw << 32) | s;
+        }
+    }
+}
+
 // ---- kad_searches_apply: add and erase searches, grow the slabs -----------------------------------
 // The new set is written beside the old one: every record and slab is gathered from src[s'] (kadplan::SRC_NEW: an
 // inserted search, zero-filled, its record from the 20 uploaded ID bytes). A streaming gather, read once with
@@ -1042,7 +1267,7 @@ int kad_searches_info(const kad_searches* ss, uint32_t* S, uint32_t* cap, uint64
     if (!ss) return set_error(KAD_ERR_INVALID, "NULL search set");
     if (S) *S = ss->S;
     if (cap) *cap = ss->cap;
-    if (device_bytes) *device_bytes = ss->bytes;
+    if (device_bytes) *device_bytes = ss->bytes + ss->mk_bytes;  // the mark scratch from its first use on
     return KAD_OK;
 }
 
@@ -1087,13 +1312,16 @@ int kad_searches_export(const kad_searches* ss, uint8_t* ids, uint8_t* flags, ui
 
 int kad_searches_destroy(kad_searches* ss) {
     if (!ss) return KAD_OK;
-    if (ss->S || ss->rf_ev[0] || ss->in_ev[0]) {  // kad_searches_apply can empty a set that holds timing events
+    if (ss->S || ss->rf_ev[0] || ss->in_ev[0] || ss->mk_ev[0] || ss->mk_buf) {  // apply can empty a set that holds events
         DeviceGuard g(ss->device);
         (void)hipDeviceSynchronize();
         for (hipEvent_t e : ss->rf_ev)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ss->in_ev)
             if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ss->mk_ev)
+            if (e) (void)hipEventDestroy(e);
+        if (ss->mk_buf) (void)hipFree(ss->mk_buf);
         free_device(ss);
     }
     delete ss;
@@ -1248,6 +1476,173 @@ int kad_sr_insert(kad_searches* ss, uint32_t m, const uint32_t* which, const uin
 int kad_sr_insert_kernel_ms(const kad_searches* ss, float* out_ms) {
     if (!ss || !out_ms) return set_error(KAD_ERR_INVALID, "NULL argument");
     *out_ms = ss->in_ms;
+    return KAD_OK;
+}
+
+int kad_sr_mark_nodes(kad_searches* ss, uint32_t q, const uint8_t* node_ids, const uint8_t* clear_bits,
+                      const uint8_t* set_bits, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids,
+                      const uint8_t* pair_flags, uint32_t* out_hits, uint8_t* out_pair_found, uint32_t* out_changed,
+                      uint8_t* out_counts, uint32_t* out_n_changed) {
+    if (!ss || !out_changed || !out_n_changed) return set_error(KAD_ERR_INVALID, "NULL argument");
+    if (q && !node_ids) return set_error(KAD_ERR_INVALID, "NULL node_ids");
+    if (p && (!pair_which || !pair_ids || !pair_flags)) return set_error(KAD_ERR_INVALID, "NULL pair arrays");
+    kadplan::SrMarkPlan plan;
+    std::string err;
+    try {
+        if (int rc = kadplan::sr_mark_plan(ss->S, q, node_ids, clear_bits, set_bits, p, pair_which, pair_ids, pair_flags,
+                                           plan, err))
+            return set_error(rc, err.c_str());
+    } catch (const std::bad_alloc&) {
+        return set_error(KAD_ERR_NOMEM, "mark: out of host memory");
+    }
+    if (q > KAD_SR_MARK_MAX_NODES) return set_error(KAD_ERR_UNSUPPORTED, "kad_sr_mark_nodes takes up to 2^20 nodes a call");
+    if (ss->cap > REFILL_MAX_CAP)
+        return set_error(KAD_ERR_UNSUPPORTED, "kad_sr_mark_nodes handles slabs of up to 64 entries");
+    *out_n_changed = 0;
+    if (out_hits && q) std::memset(out_hits, 0, 4ull * q);
+    if (out_pair_found && p) std::memset(out_pair_found, 0, p);
+    if ((q == 0 && p == 0) || ss->S == 0) return KAD_OK;
+    const uint32_t S = ss->S;
+    // The call's buffer. Up: batch keys, pair keys, batch tails, pair tails, pair searches, the batch's prefix directory,
+    // ops, pair bytes, as one copy. Back, as one copy: the count of changed searches, the hits, the first n_res (search,
+    // count word) pairs and the found bytes. More than n_res changed searches (batch nodes held by many searches each)
+    // take a second copy, of all pairs, from the handle's scratch.
+    const uint64_t want_res = 2ull * q + p + 64;
+    const uint32_t n_res = (uint32_t)(want_res < S ? want_res : S);
+    const size_t n_dir = plan.dir.size();
+    const size_t o_pkey = 8ull * q, o_btail = o_pkey + 8ull * p, o_ptail = o_btail + 12ull * q, o_pw = o_ptail + 12ull * p,
+                 o_dir = o_pw + 4ull * p, o_bop = o_dir + 4ull * n_dir, o_pfl = o_bop + q, o_out = (o_pfl + p + 7) & ~(size_t)7, o_hits = o_out + 8,
+                 o_res = (o_hits + 4ull * q + 7) & ~(size_t)7, o_found = o_res + 8ull * n_res, total = o_found + p;
+    uint8_t* h = new (std::nothrow) uint8_t[total];
+    if (!h) return set_error(KAD_ERR_NOMEM, "mark: out of host memory");
+    if (q) {
+        std::memcpy(h, plan.bkey.data(), 8ull * q);
+        std::memcpy(h + o_btail, plan.btail.data(), 12ull * q);
+        std::memcpy(h + o_bop, plan.bop.data(), q);
+        std::memcpy(h + o_dir, plan.dir.data(), 4ull * n_dir);
+    }
+    if (p) {
+        std::memcpy(h + o_pkey, plan.pkey.data(), 8ull * p);
+        std::memcpy(h + o_ptail, plan.ptail.data(), 12ull * p);
+        std::memcpy(h + o_pw, plan.pw.data(), 4ull * p);
+        std::memcpy(h + o_pfl, plan.pfl.data(), p);
+    }
+    DeviceGuard g(ss->device);
+    uint8_t* buf = nullptr;
+    auto done = [&](int r) {
+        if (buf) (void)hipFree(buf);
+        delete[] h;
+        return r;
+    };
+    if (hipDeviceSynchronize() != hipSuccess)  // queries enqueued before the call read the old set
+        return done(set_error(KAD_ERR_HIP, "mark: device in error"));
+    const size_t b_bitmap = 4ull * ((S + 31) / 32), b_scratch = MARK_HEAD_BYTES + 8ull * S + b_bitmap + 4ull * S;
+    if (ss->mk_cap < S) {  // first use, or kad_searches_apply made the set larger since
+        uint8_t* nb = nullptr;
+        if (hipMalloc((void**)&nb, b_scratch) != hipSuccess) {
+            (void)hipGetLastError();
+            return done(set_error(KAD_ERR_NOMEM, "mark: out of device memory"));
+        }
+        if (ss->mk_buf) (void)hipFree(ss->mk_buf);
+        ss->mk_buf = nb;
+        ss->mk_cap = S;
+        ss->mk_bytes = b_scratch;
+    }
+    if (hipMalloc((void**)&buf, total) != hipSuccess) {
+        (void)hipGetLastError();
+        buf = nullptr;
+        return done(set_error(KAD_ERR_NOMEM, "mark: out of device memory"));
+    }
+    for (hipEvent_t& e : ss->mk_ev)
+        if (!e && hipEventCreate(&e) != hipSuccess) return done(set_error(KAD_ERR_HIP, "mark: no events"));
+    // the scratch is laid out for mk_cap searches; only the part of the current S is used
+    const size_t cap_bitmap = 4ull * (((size_t)ss->mk_cap + 31) / 32);
+    // the count, the (search, count word) pairs of the last call, the bitmap, the list
+    uint32_t* d_head = (uint32_t*)ss->mk_buf;
+    uint64_t* d_all = (uint64_t*)(ss->mk_buf + MARK_HEAD_BYTES);
+    uint32_t* d_bitmap = (uint32_t*)(ss->mk_buf + MARK_HEAD_BYTES + 8ull * ss->mk_cap);
+    uint32_t* d_list = (uint32_t*)(ss->mk_buf + MARK_HEAD_BYTES + 8ull * ss->mk_cap + cap_bitmap);
+    if (hipMemcpy(buf, h, o_out, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemsetAsync(d_head, 0, MARK_HEAD_BYTES, nullptr) != hipSuccess ||
+        hipMemsetAsync(d_bitmap, 0, b_bitmap, nullptr) != hipSuccess ||
+        hipMemsetAsync(buf + o_out, 0, total - o_out, nullptr) != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, "mark: H2D failed"));
+    const DevMark D{ss->rec, ss->mkey, ss->mtail, ss->mflag, S, ss->cap, S * ss->cap, q, (const uint64_t*)buf,
+                    (const uint32_t*)(buf + o_btail), buf + o_bop, (const uint32_t*)(buf + o_dir), 64u - plan.dbits, p,
+                    (const uint32_t*)(buf + o_pw),
+                    (const uint64_t*)(buf + o_pkey), (const uint32_t*)(buf + o_ptail), buf + o_pfl,
+                    out_hits ? (uint32_t*)(buf + o_hits) : nullptr, buf + o_found, d_head, d_bitmap, d_list};
+    hipError_t le = hipSuccess;
+    (void)hipEventRecord(ss->mk_ev[0], nullptr);
+    if (q) {
+        const uint32_t blocks = (D.total + BLOCK - 1) / BLOCK, grid = blocks < MAX_GRID ? blocks : MAX_GRID;
+        if (q <= MARK_LDS_KEYS)
+            hipLaunchKernelGGL(mark_scan_kernel<true>, dim3(grid), dim3(BLOCK), 0, nullptr, D);
+        else
+            hipLaunchKernelGGL(mark_scan_kernel<false>, dim3(grid), dim3(BLOCK), 0, nullptr, D);
+        le = hipGetLastError();
+    }
+    (void)hipEventRecord(ss->mk_ev[1], nullptr);
+    if (le == hipSuccess && p) {
+        hipLaunchKernelGGL(mark_pairs_kernel, dim3((p + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, D);
+        le = hipGetLastError();
+    }
+    (void)hipEventRecord(ss->mk_ev[2], nullptr);
+    if (le == hipSuccess) {  // the grid is sized without the count: the waves stride over what the head word says
+        const uint32_t blocks = (S + REFILL_WAVES - 1) / REFILL_WAVES, grid = blocks < MARK_FIX_GRID ? blocks : MARK_FIX_GRID;
+        hipLaunchKernelGGL(mark_fix_kernel, dim3(grid), dim3(BLOCK), 0, nullptr, D, d_all, (uint32_t*)(buf + o_out),
+                           (uint64_t*)(buf + o_res), n_res);
+        le = hipGetLastError();
+    }
+    (void)hipEventRecord(ss->mk_ev[3], nullptr);
+    if (le != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, (std::string("mark: launch failed: ") + hipGetErrorString(le)).c_str()));
+    const hipError_t ce = hipMemcpy(h + o_out, buf + o_out, total - o_out, hipMemcpyDeviceToHost);
+    if (ce != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, (std::string("mark: D2H failed: ") + hipGetErrorString(ce)).c_str()));
+    if (hipEventElapsedTime(&ss->mk_ms[0], ss->mk_ev[0], ss->mk_ev[1]) != hipSuccess ||
+        hipEventElapsedTime(&ss->mk_ms[1], ss->mk_ev[2], ss->mk_ev[3]) != hipSuccess) {
+        (void)hipGetLastError();
+        ss->mk_ms[0] = ss->mk_ms[1] = 0.f;
+    }
+    uint32_t n_changed;
+    std::memcpy(&n_changed, h + o_out, 4);
+    if (n_changed > S) return done(set_error(KAD_ERR_HIP, "mark: changed count out of range"));
+    std::vector<uint64_t> res;  // count word << 32 | search: the search is what the sort goes by
+    try {
+        res.resize(n_changed);
+        if (n_changed <= n_res) {
+            if (n_changed) std::memcpy(res.data(), h + o_res, 8ull * n_changed);
+        } else {
+            if (hipMemcpy(res.data(), d_all, 8ull * n_changed, hipMemcpyDeviceToHost) != hipSuccess)
+                return done(set_error(KAD_ERR_HIP, "mark: D2H of the changed list failed"));
+        }
+    } catch (const std::bad_alloc&) {
+        return done(set_error(KAD_ERR_NOMEM, "mark: out of host memory"));
+    }
+    std::sort(res.begin(), res.end(), [](uint64_t a, uint64_t b) { return (uint32_t)a < (uint32_t)b; });
+    for (uint32_t k = 0; k < n_changed; k++) {
+        out_changed[k] = (uint32_t)res[k];
+        if (out_counts) {
+            const uint32_t c = (uint32_t)(res[k] >> 32);
+            out_counts[4ull * k] = (uint8_t)c;
+            out_counts[4ull * k + 1] = (uint8_t)(c >> 8);
+            out_counts[4ull * k + 2] = (uint8_t)(c >> 16);
+            out_counts[4ull * k + 3] = (uint8_t)(c >> 24);
+        }
+    }
+    if (out_hits)
+        for (uint32_t j = 0; j < q; j++) std::memcpy(out_hits + plan.ord[j], h + o_hits + 4ull * j, 4);
+    if (out_pair_found)
+        for (uint32_t k = 0; k < p; k++) out_pair_found[plan.pord[k]] = h[o_found + k];
+    *out_n_changed = n_changed;
+    return done(KAD_OK);
+}
+
+int kad_sr_mark_kernel_ms(const kad_searches* ss, float* out_scan_ms, float* out_fix_ms) {
+    if (!ss || !out_scan_ms || !out_fix_ms) return set_error(KAD_ERR_INVALID, "NULL argument");
+    *out_scan_ms = ss->mk_ms[0];
+    *out_fix_ms = ss->mk_ms[1];
     return KAD_OK;
 }
 

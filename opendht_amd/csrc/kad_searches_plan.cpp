@@ -176,6 +176,76 @@ int sr_insert_check(uint32_t S, uint32_t m, const uint32_t* which, const uint32_
     return KAD_OK;
 }
 
+int sr_mark_plan(uint32_t S, uint32_t q, const uint8_t* node_ids, const uint8_t* clear_bits, const uint8_t* set_bits,
+                 uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids, const uint8_t* pair_flags,
+                 SrMarkPlan& out, std::string& err) {
+    constexpr uint8_t known = KAD_SN_BAD | KAD_SN_REMOVABLE;
+    for (uint32_t j = 0; clear_bits && j < q; j++)
+        if (clear_bits[j] & ~known) return fail(err, KAD_ERR_INVALID, "node %u: unknown bit in clear_bits", j);
+    for (uint32_t j = 0; set_bits && j < q; j++)
+        if (set_bits[j] & ~known) return fail(err, KAD_ERR_INVALID, "node %u: unknown bit in set_bits", j);
+    for (uint32_t k = 0; k < p; k++)
+        if (pair_flags[k] & ~known) return fail(err, KAD_ERR_INVALID, "pair %u: unknown bit in pair_flags", k);
+    for (uint32_t j = 0; clear_bits && set_bits && j < q; j++)
+        if (clear_bits[j] & set_bits[j]) return fail(err, KAD_ERR_INVALID, "node %u: a bit both cleared and set", j);
+    out.ord.resize(q);
+    for (uint32_t j = 0; j < q; j++) out.ord[j] = j;
+    // big-endian bytes: memcmp order is (key, tail) order
+    std::sort(out.ord.begin(), out.ord.end(), [&](uint32_t a, uint32_t b) {
+        return std::memcmp(node_ids + 20ull * a, node_ids + 20ull * b, KAD_HASH_LEN) < 0;
+    });
+    for (uint32_t j = 1; j < q; j++)
+        if (std::memcmp(node_ids + 20ull * out.ord[j - 1], node_ids + 20ull * out.ord[j], KAD_HASH_LEN) == 0)
+            return fail(err, KAD_ERR_INVALID, "node IDs %u and %u are equal", out.ord[j - 1], out.ord[j]);
+    for (uint32_t k = 0; k < p; k++)
+        if (pair_which[k] >= S) return fail(err, KAD_ERR_INVALID, "pair %u: search %u not below S", k, pair_which[k]);
+    out.pord.resize(p);
+    for (uint32_t k = 0; k < p; k++) out.pord[k] = k;
+    std::sort(out.pord.begin(), out.pord.end(), [&](uint32_t a, uint32_t b) {
+        if (pair_which[a] != pair_which[b]) return pair_which[a] < pair_which[b];
+        return std::memcmp(pair_ids + 20ull * a, pair_ids + 20ull * b, KAD_HASH_LEN) < 0;
+    });
+    for (uint32_t k = 1; k < p; k++) {
+        const uint32_t a = out.pord[k - 1], b = out.pord[k];
+        if (pair_which[a] == pair_which[b] && std::memcmp(pair_ids + 20ull * a, pair_ids + 20ull * b, KAD_HASH_LEN) == 0)
+            return fail(err, KAD_ERR_INVALID, "pairs %u and %u are equal", a, b);
+    }
+    out.bkey.resize(q);
+    out.btail.resize(3ull * q);
+    out.bop.resize(q);
+    for (uint32_t j = 0; j < q; j++) {
+        const uint32_t a = out.ord[j];
+        const uint8_t* id = node_ids + 20ull * a;
+        out.bkey[j] = top64(id);
+        for (int w = 0; w < 3; w++) out.btail[3ull * j + w] = be32(id + 8 + 4 * w);
+        out.bop[j] = (uint8_t)((clear_bits ? clear_bits[a] : 0) | ((set_bits ? set_bits[a] : 0) << 2));
+    }
+    out.dir.clear();
+    out.dbits = 0;
+    if (q) {
+        const uint32_t most = q <= SR_MARK_SMALL_BATCH ? SR_MARK_DIR_BITS_SMALL : SR_MARK_DIR_BITS;
+        uint32_t B = 1;
+        while (B < most && (1u << B) < q) B++;
+        out.dbits = B;
+        out.dir.assign(((size_t)1 << B) + 1, 0u);
+        for (uint32_t j = 0; j < q; j++) out.dir[(size_t)(out.bkey[j] >> (64 - B)) + 1]++;
+        for (size_t s = 1; s < out.dir.size(); s++) out.dir[s] += out.dir[s - 1];
+    }
+    out.pw.resize(p);
+    out.pkey.resize(p);
+    out.ptail.resize(3ull * p);
+    out.pfl.resize(p);
+    for (uint32_t k = 0; k < p; k++) {
+        const uint32_t a = out.pord[k];
+        const uint8_t* id = pair_ids + 20ull * a;
+        out.pw[k] = pair_which[a];
+        out.pkey[k] = top64(id);
+        for (int w = 0; w < 3; w++) out.ptail[3ull * k + w] = be32(id + 8 + 4 * w);
+        out.pfl[k] = pair_flags[a];
+    }
+    return KAD_OK;
+}
+
 }  // namespace kadplan
 
 extern "C" int kad_search_trim(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t* full,

@@ -62,4 +62,35 @@ int searches_apply_plan(uint32_t S, const uint8_t* ids, const uint32_t* erase, u
 int sr_insert_check(uint32_t S, uint32_t m, const uint32_t* which, const uint32_t* off, const uint8_t* cand_flags,
                     std::string& err);
 
+// The prefix directory of a batch of up to SR_MARK_SMALL_BATCH keys has at most 2^11 + 1 slots (it is staged next to the
+// keys in the scan kernel's LDS), that of a larger batch at most 2^16 + 1.
+constexpr uint32_t SR_MARK_SMALL_BATCH = 4096, SR_MARK_DIR_BITS_SMALL = 11, SR_MARK_DIR_BITS = 16;
+
+// Host plan of kad_sr_mark_nodes: the batch of changed nodes sorted by (key, tail) and the pair
+// overrides sorted by (search, ID), in the device's word form, with the permutations that bring the per-node and
+// per-pair outputs back into the caller's order. The prefix directory over the sorted keys lets the scan
+// kernel find a member key's bucket with two reads; within the bucket it searches as before, so keys that crowd one
+// prefix cost time, never correctness.
+struct SrMarkPlan {
+    std::vector<uint32_t> ord;    // q: sorted position -> the caller's node index
+    std::vector<uint64_t> bkey;   // q keys (top 64 bits of the ID), ascending
+    std::vector<uint32_t> btail;  // q x 3 tails
+    std::vector<uint8_t> bop;     // q: clear_bits | set_bits << 2
+    std::vector<uint32_t> dir;    // 2^B + 1: dir[p] = the batch keys whose top B bits are below p (empty for q == 0)
+    uint32_t dbits = 0;           // B = ceil(log2 q) within [1, SR_MARK_DIR_BITS_SMALL or SR_MARK_DIR_BITS]
+    std::vector<uint32_t> pord;   // p: sorted position -> the caller's pair index
+    std::vector<uint32_t> pw;     // p search indices, ascending
+    std::vector<uint64_t> pkey;   // p keys, p x 3 tails: ascending IDs within one search
+    std::vector<uint32_t> ptail;
+    std::vector<uint8_t> pfl;     // p: the exact flag byte
+};
+
+// node_ids: q x 20 B in any order; clear_bits / set_bits: q bytes each or NULL (all zero); pair_which / pair_ids /
+// pair_flags: p pairs in any order. Checked in this order, all KAD_ERR_INVALID with `err` set: a bit other than
+// KAD_SN_BAD | KAD_SN_REMOVABLE in clear_bits, set_bits or pair_flags; clear_bits[j] & set_bits[j] != 0; two equal node
+// IDs; pair_which[k] >= S; two equal (search, ID) pairs. q == 0 and p == 0 read nothing. O(q log q + p log p).
+int sr_mark_plan(uint32_t S, uint32_t q, const uint8_t* node_ids, const uint8_t* clear_bits, const uint8_t* set_bits,
+                 uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids, const uint8_t* pair_flags,
+                 SrMarkPlan& out, std::string& err);
+
 }  // namespace kadplan

@@ -6,6 +6,8 @@ whole tick of candidates and one snapshot of the searches, which searches would 
 walk stopped; try_search_insert turns those verdicts into the exact sequential result while the host touches only
 the searches that accept. try_search_insert_device goes one step further: the accepted inserts
 run on the device as well (kad_sr_insert), in rounds planned by plan_insert_round, and no list is uploaded.
+mark_search_nodes carries the node status changes of a tick (timeouts, replies, candidate bits) to
+every list that holds the node with one kad_sr_mark_nodes, without the host looking for the holders.
 """
 from __future__ import annotations
 
@@ -13,7 +15,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (KAD_NO_NODE, KAD_SEARCH_NODES, KAD_SN_BAD, KAD_SR_INSERT_OVERFLOW, KAD_SR_REFILL_OVERFLOW,
+from ._lib import (KAD_NO_NODE, KAD_SEARCH_NODES, KAD_SN_BAD, KAD_SN_REMOVABLE, KAD_SR_INSERT_OVERFLOW,
+                   KAD_SR_REFILL_OVERFLOW,
                    KAD_SR_STOP_END, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED, KAD_SR_STOP_KNOWN, check, lib, ptr)
 from .table import _as_ids, _stream_of
 
@@ -205,6 +208,43 @@ class DeviceSearches:
         ms = C.c_float()
         check(lib().kad_sr_insert_kernel_ms(self._h, C.byref(ms)), "kad_sr_insert_kernel_ms")
         return ms.value
+
+    def mark_nodes(self, node_ids, clear_bits=None, set_bits=None, pairs=None) -> dict:
+        """Node status changes over the set (kad_sr_mark_nodes): every list entry whose ID is node_ids[j] ((q, 20) uint8,
+        distinct, any order) gets the flag byte (f & ~clear_bits[j]) | set_bits[j] ((q,) uint8 of KAD_SN_BAD |
+        KAD_SN_REMOVABLE, None for all zero); then every pair of pairs = (which (p,), ids (p, 20), flags (p,)) whose
+        search holds the ID gets exactly its flag byte. Returns hits (q,) uint32 (searches that hold node j), pair_found
+        (p,) uint8, changed (ascending indices of the searches with a byte that differs from before) and counts
+        (len(changed), 4) uint8: n, bad, leading bad, record bits. Synchronous."""
+        ids = _as_ids(node_ids) if len(node_ids) else np.zeros((0, 20), np.uint8)
+        q = ids.shape[0]
+        if clear_bits is not None:
+            clear_bits = np.ascontiguousarray(clear_bits, dtype=np.uint8).reshape(-1)
+        if set_bits is not None:
+            set_bits = np.ascontiguousarray(set_bits, dtype=np.uint8).reshape(-1)
+        if any(b is not None and b.shape[0] != q for b in (clear_bits, set_bits)):
+            raise ValueError("clear_bits / set_bits must have one byte per node")
+        pw, pid, pfl, p = None, None, None, 0
+        if pairs is not None and len(pairs[0]):
+            pw = np.ascontiguousarray(pairs[0], dtype=np.uint32).reshape(-1)
+            pid = _as_ids(pairs[1])
+            pfl = np.ascontiguousarray(pairs[2], dtype=np.uint8).reshape(-1)
+            p = pw.shape[0]
+            if pid.shape[0] != p or pfl.shape[0] != p:
+                raise ValueError("pairs must be (which, ids, flags) of one length")
+        hits, found = np.zeros(q, np.uint32), np.zeros(p, np.uint8)
+        changed, counts, n = np.zeros(self.S, np.uint32), np.zeros((self.S, 4), np.uint8), C.c_uint32()
+        check(lib().kad_sr_mark_nodes(self._h, q, ptr(ids), ptr(clear_bits), ptr(set_bits), p, ptr(pw), ptr(pid),
+                                      ptr(pfl), ptr(hits), ptr(found), ptr(changed), ptr(counts), C.byref(n)),
+              "kad_sr_mark_nodes")
+        return {"hits": hits, "pair_found": found, "changed": changed[:n.value].copy(),
+                "counts": counts[:n.value].copy()}
+
+    def mark_kernel_ms(self):
+        """The device times (scan kernel, fix kernel) of the last mark_nodes (kad_sr_mark_kernel_ms)."""
+        a, b = C.c_float(), C.c_float()
+        check(lib().kad_sr_mark_kernel_ms(self._h, C.byref(a), C.byref(b)), "kad_sr_mark_kernel_ms")
+        return a.value, b.value
 
     @property
     def refill_kernel_ms(self) -> float:
@@ -492,6 +532,49 @@ def try_search_insert_device(DS, host, cand_ids, now, max_rounds=8) -> dict:
                 dirty += holders
         _patch_from_host(DS, host, dirty, now)
     return counts
+
+
+SEARCH_MAX_BAD_NODES = 25  # dht.h:324
+
+
+def mark_search_nodes(DS, host, nodes, pairs, now) -> dict:
+    """The status changes of one tick carried to the device set with one DS.mark_nodes. nodes: the
+    nodes whose isExpired() or time changed (any handles the host understands, one per ID); pairs: (search index, node)
+    for every list entry whose `candidate` changed, or whose node un-expired while `candidate` is set. `host` holds the
+    real searches: node_id(x) -> the 20 ID bytes, expired(x) -> node->isExpired(), removable(x, now) -> expired and
+    time + NODE_EXPIRE_TIME < now, pair_flag(s, x, now) -> the flag byte of x in search s (KAD_SN_BAD from
+    SearchNode::isBad(), KAD_SN_REMOVABLE as above). An expired node gives set BAD plus set or clear REMOVABLE at `now`,
+    a live node clears both; an entry that is a candidate of its search needs its pair, as its BAD bit is not the node's.
+
+    Returns the changed searches split by what Dht::searchStep would do with them next, from the counts alone: "expire"
+    (leading bad entries >= min(n, SEARCH_MAX_BAD_NODES), dht.cpp:1451), else "short" (n - bad < SEARCH_NODES, the
+    refill test of :1354), else "neither"; plus "hits" and "pair_found" as mark_nodes gives them."""
+    both = KAD_SN_BAD | KAD_SN_REMOVABLE
+    ids = np.zeros((len(nodes), 20), np.uint8)
+    clear, setb = np.zeros(len(nodes), np.uint8), np.zeros(len(nodes), np.uint8)
+    for j, x in enumerate(nodes):
+        ids[j] = np.frombuffer(bytes(host.node_id(x)), np.uint8)
+        if host.expired(x):
+            setb[j] = both if host.removable(x, now) else KAD_SN_BAD
+            clear[j] = both & ~setb[j]
+        else:
+            clear[j] = both
+    pw = np.array([s for s, _ in pairs], np.uint32)
+    pid = np.zeros((len(pairs), 20), np.uint8)
+    pfl = np.zeros(len(pairs), np.uint8)
+    for k, (s, x) in enumerate(pairs):
+        pid[k] = np.frombuffer(bytes(host.node_id(x)), np.uint8)
+        pfl[k] = host.pair_flag(int(s), x, now)
+    r = DS.mark_nodes(ids, clear, setb, (pw, pid, pfl))
+    out = {"expire": [], "short": [], "neither": [], "hits": r["hits"], "pair_found": r["pair_found"]}
+    for s, (n, bad, lead, _) in zip(r["changed"], r["counts"]):
+        if int(lead) >= min(int(n), SEARCH_MAX_BAD_NODES):
+            out["expire"].append(int(s))
+        elif int(n) - int(bad) < KAD_SEARCH_NODES:
+            out["short"].append(int(s))
+        else:
+            out["neither"].append(int(s))
+    return out
 
 
 def refill_searches(DS: DeviceSearches, NC, host, which, now) -> dict:
