@@ -985,10 +985,12 @@ int kad_search_create(kad_search** out, const kad_swarm* s, uint32_t S, const ui
 int kad_search_hop(kad_search* x, uint32_t* n_active);
 /* Host outputs (any may be NULL): list S x KAD_SEARCH_LIST peer indices (KAD_NO_NODE padded), queried and
  * bad flags S x KAD_SEARCH_LIST, list length S, hops S, done S (0 running, 1 synced: the first 8 non-bad
- * nodes answered, 2 stalled, 3 expired: the first min(size, 25) nodes are bad), overflow (1 value: lists that
- * reached KAD_SEARCH_LIST entries). */
+ * nodes answered, 2 stalled, 3 expired: the first min(size, 25) nodes are bad), overflow (1 value: the lookups
+ * and hops so far in which a capacity was hit — a list of KAD_SEARCH_LIST entries had to take one more, or a
+ * lookup met more than 64 silent peers; the rule is in kad_swarm.hip's header). */
 int kad_search_get(const kad_search* x, uint32_t* list, uint8_t* queried, uint8_t* bad, uint8_t* n, uint32_t* hops,
                    uint8_t* done, uint32_t* overflow);
+/* Hands the search's device state to its swarm's pool: destroy a search before its swarm. */
 int kad_search_destroy(kad_search* x);
 
 /* ---- InfoHash primitives (infohash.h), batched, device pointers ---------- */

@@ -15,6 +15,13 @@
 //     go through Search::insertNode (dht.cpp:961-1047: sorted insert, trim to SEARCH_NODES = 14).
 //     Done when the first min(8, |list|) nodes have been queried (Search::isSynced, dht.cpp:1467-1478);
 //     stalled when no unqueried node is left.
+//   * capacities (the oracle's list_cap = 32 and silent_cap = 64; its own lists are unbounded without them): a
+//     lookup's list holds at most KAD_SEARCH_LIST entries. A node that passed insertNode's checks and meets a list
+//     of KAD_SEARCH_LIST entries leaves the list holding the KAD_SEARCH_LIST closest of its entries and the node: a
+//     node that sorts after every entry is refused and the list stays whole; otherwise the farthest entry goes and
+//     the node is inserted at its place. A lookup remembers at most XO_CAP silent peers: one past that still turns
+//     the list entries naming it bad, but is not remembered, so a later answer naming it joins the list as a
+//     non-bad node. Either event counts once per lookup and hop (kad_search_get's overflow).
 //
 // HBM layout (n peers, L = KAD_SWARM_LEVELS levels, 8 entries per bucket):
 //   key[n] u64 (ID bits 0..63 of the sorted peer IDs), tail[n][3] u32 (bits 64..159, exact ties only)
@@ -427,7 +434,7 @@ struct SearchDev {
     uint64_t* rk;
     uint8_t* rn;    // [S][ALPHA]
     uint32_t* active;
-    uint32_t* overflow;  // lists that hit LST entries (a bad node was dropped from the end)
+    uint32_t* overflow;  // lookups and hops in which a capacity (LST entries, XO_CAP silent peers) was hit
     uint32_t* xo;   // [S][XO_CAP] the search's queried peers that stayed silent: their nodes are expired
     uint8_t* xn;    // [S] how many
     uint32_t S;
@@ -566,7 +573,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SW_QUERY_
     X.rn[g] = (uint8_t)m;
 }
 
-constexpr uint32_t XO_CAP = 64;  // silent peers remembered per lookup (4 per hop; beyond it: counted in overflow)
+constexpr uint32_t XO_CAP = 64;  // silent peers remembered per lookup (4 per hop; beyond it: counted in overflow;
+                                 // the most any test's lookup meets is 62)
 
 // Search::insertNode of node r at top-64 distance rd (dht.cpp:961-1047, expired search = false); rbad: r's node
 // is expired (a peer this search queried and that stayed silent), so it joins the list as a bad node
@@ -619,11 +627,11 @@ __device__ __forceinline__ void search_insert(const SwarmDev& W, const Tgt& t, u
         bad = (uint32_t)__builtin_popcount(bm & lo_mask(n));
         if (pos >= tt) return;
     }
-    if (n == N) {  // capacity: drop the farthest entry (counted; never reached in the tests)
-        bad -= (bm >> (N - 1)) & 1u;
-        n--;
+    if (n == N) {  // capacity (the header's rule; counted): the list keeps the N closest of its entries and r
         ovf = true;
-        if (pos >= n) return;
+        if (pos >= N) return;  // r is the farthest: refused, the list stays whole
+        bad -= (bm >> (N - 1)) & 1u;
+        n--;  // the farthest entry goes (its flag bits are shifted out by the insert below)
     }
     // insert at pos: entries from pos on move up one (selects, not conditional stores: those became stores through
     // a selected pointer and put the lists in scratch); entries from n + 1 on are don't-care
@@ -799,7 +807,9 @@ __device__ __forceinline__ bool merge_lookup(const SwarmDev& W, const SearchDev&
 // compares), is re-sorted (19 compare-exchanges), and merges with the 16-slot list as one bitonic half-cleaner (the
 // list ascending, the block descending) and four levels: ~560 VALU operations a block where the sequential inserts
 // took ~250 each answer. Equal 64-bit distances of different nodes (their order needs the 160-bit tails) are adjacent
-// after each merge; a lookup that has one is left untouched with done = 4 and the sequential form merges it next.
+// after each merge; a lookup that has one is left untouched with done = 4 and the sequential form merges it next. So
+// is a lookup with an answer at top-64 distance ~0, the empty slots' key (the target's top 64 bits are the complement
+// of the node's): the network cannot tell it from a hole.
 // Queried flags travel in bit 31 of the node index.
 // PF: the next queried node's answers loaded before the current block is merged (a second Answers in registers).
 template <bool PF>
@@ -851,6 +861,7 @@ __device__ __forceinline__ bool merge_lookup_net(const SwarmDev& W, const Search
             for (uint32_t k = 0; k < 16; k++) drop |= (li[k] & IM) == r;  // already in the list (empty slots: IM)
             bk[j] = drop ? MAXK : A.k[j] ^ t.hi;
             bi[j] = drop ? NONE : r;
+            tie |= !drop && bk[j] == MAXK;  // (a new node as far as the padding: the network would leave it out)
         }
         sort8_kid(bk, bi);  // (the block was sorted; the dropped entries leave MAX holes)
         // the 16 smallest of (list ascending, block descending): one half-cleaner, then four levels

@@ -4,6 +4,7 @@ model in opendht_amd/csrc/kad_swarm.hip). Thin plumbing for tests and tools/benc
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -22,9 +23,14 @@ class Swarm:
         h = C.c_void_p()
         check(lib().kad_swarm_create(C.byref(h), device, self.n, ptr(ids)), "kad_swarm_create")
         self._h = h
+        self._searches = weakref.WeakSet()
 
     def close(self):
+        """Destroys the swarm, after the searches still open on it: a search reads its swarm's tables and hands its
+        device state to the swarm's pool when it is destroyed, so it must not outlive the swarm (kadgpu.h)."""
         if getattr(self, "_h", None):
+            for x in list(self._searches):
+                x.close()
             lib().kad_swarm_destroy(self._h)
             self._h = None
 
@@ -79,6 +85,7 @@ class Search:
         check(lib().kad_search_create(C.byref(h), swarm._h, self.S, ptr(src), ptr(targets), offline_per_10k, s),
               "kad_search_create")
         self._h = h
+        swarm._searches.add(self)
 
     def hop(self) -> int:
         a = C.c_uint32()

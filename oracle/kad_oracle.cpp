@@ -769,10 +769,19 @@ static inline bool swarm_offline(uint32_t p, uint32_t per10k) {
     return per10k && (uint32_t)(sw_mix((uint64_t)p * 0x9E37ull + 0xBADull) % 10000ull) < per10k;
 }
 
-int orc_swarm_search_ex(void* h, uint32_t S, const uint32_t* src, const uint8_t* targets, uint32_t max_hops,
-                        uint32_t offline_per_10k, uint32_t* out_list, uint8_t* out_q, uint8_t* out_bad, uint8_t* out_n,
-                        uint32_t* out_hops, uint8_t* out_done, int nthreads) {
-    const Swarm* s = (const Swarm*)h;
+// Capacities (the device's: kad_swarm.hip keeps a lookup's list in KAD_SEARCH_LIST = 32 slots and remembers at
+// most 64 silent peers; 0 = unbounded, this model's own form):
+//   list_cap: a node that passed insertNode's checks and meets a list of list_cap entries leaves the list holding
+//   the list_cap closest of its entries and the node: a node that sorts after every entry is refused and the list
+//   stays whole; otherwise the farthest entry goes and the node is inserted at its place.
+//   silent_cap: a lookup remembers at most silent_cap silent peers: one past that still turns the list entries
+//   naming it bad, but is not remembered, so a later answer naming it joins the list as a non-bad node.
+//   Either event counts once per lookup and hop (out_cap_hops).
+// out_peak: the longest list right after any insert (or the seed); out_silent: the silent peers remembered.
+static int swarm_search_run(const Swarm* s, uint32_t S, const uint32_t* src, const uint8_t* targets, uint32_t max_hops,
+                            uint32_t offline_per_10k, uint32_t list_cap, uint32_t silent_cap, uint32_t* out_list,
+                            uint8_t* out_q, uint8_t* out_bad, uint8_t* out_n, uint32_t* out_hops, uint8_t* out_done,
+                            uint32_t* out_peak, uint32_t* out_silent, uint32_t* out_cap_hops, int nthreads) {
     struct SN { uint32_t idx; uint8_t queried, bad; };
     parallel_for(S, nthreads, [&](uint32_t a, uint32_t e) {
       for (uint32_t i = a; i < e; i++) {
@@ -786,6 +795,9 @@ int orc_swarm_search_ex(void* h, uint32_t S, const uint32_t* src, const uint8_t*
         auto id_of = [&](uint32_t v) { return Id(s->ids + (size_t)HASH_LEN * v); };
         // the peers this search queried that stayed silent: their nodes are expired from then on
         std::vector<uint32_t> silent;
+        size_t peak = L.size();
+        uint32_t cap_hops = 0;
+        bool cap_hit = false;  // a capacity was hit in the current hop
         // Search::insertNode(node) (dht.cpp:961-1047, expired search = false); an expired node joins as a bad
         // search node (`if (node.isExpired()) bad++`, :1023-1025)
         auto insert = [&](uint32_t r) {
@@ -810,8 +822,15 @@ int orc_swarm_search_ex(void* h, uint32_t S, const uint32_t* src, const uint8_t*
                 if (tt != L.size()) L.resize(tt);
                 if (n >= tt) return;
             }
+            if (list_cap && L.size() >= list_cap) {  // the list keeps the list_cap closest of its entries and r
+                cap_hit = true;
+                if (n >= L.size()) return;  // r is the farthest
+                if (L.back().bad) bad--;
+                L.pop_back();
+            }
             const bool rbad = std::find(silent.begin(), silent.end(), r) != silent.end();
             L.insert(L.begin() + n, SN{r, 0, (uint8_t)(rbad ? 1 : 0)});
+            peak = std::max(peak, L.size());
             bad += rbad ? 1 : 0;
             while (L.size() - bad > SW_SEARCH) {
                 if (L.back().bad) bad--;
@@ -828,6 +847,7 @@ int orc_swarm_search_ex(void* h, uint32_t S, const uint32_t* src, const uint8_t*
         select();
         while (!done && hops < max_hops) {
             hops++;
+            cap_hit = false;
             std::vector<uint32_t> rep;
             for (uint32_t v : sel) {
                 if (swarm_offline(v, offline_per_10k)) continue;  // no answer this hop
@@ -837,10 +857,12 @@ int orc_swarm_search_ex(void* h, uint32_t S, const uint32_t* src, const uint8_t*
             }
             for (uint32_t v : sel)  // the silent ones: expired after their tries, bad search nodes
                 if (swarm_offline(v, offline_per_10k)) {
-                    silent.push_back(v);
+                    if (!silent_cap || silent.size() < silent_cap) silent.push_back(v);
+                    else cap_hit = true;
                     for (SN& x : L)
                         if (x.idx == v) x.bad = 1;
                 }
+            cap_hops += cap_hit ? 1 : 0;
             uint32_t good = 0;  // Search::isSynced
             bool synced = true;
             for (const SN& x : L) {
@@ -862,9 +884,29 @@ int orc_swarm_search_ex(void* h, uint32_t S, const uint32_t* src, const uint8_t*
         out_n[i] = (uint8_t)std::min<size_t>(L.size(), 255);
         out_hops[i] = hops;
         out_done[i] = done;
+        if (out_peak) out_peak[i] = (uint32_t)peak;
+        if (out_silent) out_silent[i] = (uint32_t)silent.size();
+        if (out_cap_hops) out_cap_hops[i] = cap_hops;
       }
     });
     return 0;
+}
+
+int orc_swarm_search_ex(void* h, uint32_t S, const uint32_t* src, const uint8_t* targets, uint32_t max_hops,
+                        uint32_t offline_per_10k, uint32_t* out_list, uint8_t* out_q, uint8_t* out_bad, uint8_t* out_n,
+                        uint32_t* out_hops, uint8_t* out_done, int nthreads) {
+    return swarm_search_run((const Swarm*)h, S, src, targets, max_hops, offline_per_10k, 0, 0, out_list, out_q, out_bad,
+                            out_n, out_hops, out_done, nullptr, nullptr, nullptr, nthreads);
+}
+
+// orc_swarm_search_ex under the device's two capacities (0 = unbounded), with each lookup's peak list length, silent
+// peers remembered and hops in which a capacity was hit.
+int orc_swarm_search_cap(void* h, uint32_t S, const uint32_t* src, const uint8_t* targets, uint32_t max_hops,
+                         uint32_t offline_per_10k, uint32_t list_cap, uint32_t silent_cap, uint32_t* out_list,
+                         uint8_t* out_q, uint8_t* out_bad, uint8_t* out_n, uint32_t* out_hops, uint8_t* out_done,
+                         uint32_t* out_peak, uint32_t* out_silent, uint32_t* out_cap_hops, int nthreads) {
+    return swarm_search_run((const Swarm*)h, S, src, targets, max_hops, offline_per_10k, list_cap, silent_cap, out_list,
+                            out_q, out_bad, out_n, out_hops, out_done, out_peak, out_silent, out_cap_hops, nthreads);
 }
 
 // All peers online (the round-1 interface): lists of SEARCH_NODES.

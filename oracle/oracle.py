@@ -49,6 +49,8 @@ _SIG = {
     "orc_swarm_closest": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.c_int]),
     "orc_swarm_search": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, C.c_int]),
     "orc_swarm_search_ex": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_int]),
+    "orc_swarm_search_cap": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P,
+                                       _P, _P, _P, _P, _P, _P, C.c_int]),
 }
 _lib = None
 
@@ -249,6 +251,7 @@ def parse_nodes(records, rec_len, myid):
 
 
 SW_LEVELS, SW_BUCKET, SW_SEARCH, SW_LIST = 28, 8, 14, 32
+SW_SILENT = 64  # kad_swarm.hip XO_CAP
 
 
 class SwarmModel:
@@ -317,6 +320,25 @@ class SwarmModel:
         lib().orc_swarm_search_ex(self._h, S, _p(src), _p(t), max_hops, offline_per_10k, _p(lst), _p(qf), _p(bad),
                                   _p(n), _p(hops), _p(done), nthreads)
         return lst, qf, bad, n, hops, done
+
+    def search_cap(self, src, targets, offline_per_10k, list_cap=SW_LIST, silent_cap=SW_SILENT, max_hops=64, nthreads=8):
+        """search_ex under the device's two capacities (kad_oracle.cpp swarm_search_run; 0 = unbounded): (list, queried,
+        bad, n, hops, done, peak, silent, cap_hops), the last three per lookup: the longest list right after any
+        insert, the silent peers remembered, and the hops in which a capacity was hit."""
+        src = np.ascontiguousarray(src, np.uint32)
+        t = _ids(targets)
+        S = src.shape[0]
+        lst = np.empty((S, SW_LIST), np.uint32)
+        qf = np.empty((S, SW_LIST), np.uint8)
+        bad = np.empty((S, SW_LIST), np.uint8)
+        n = np.empty((S,), np.uint8)
+        hops = np.empty((S,), np.uint32)
+        done = np.empty((S,), np.uint8)
+        peak, silent, cap_hops = (np.empty((S,), np.uint32) for _ in range(3))
+        lib().orc_swarm_search_cap(self._h, S, _p(src), _p(t), max_hops, offline_per_10k, list_cap, silent_cap, _p(lst),
+                                   _p(qf), _p(bad), _p(n), _p(hops), _p(done), _p(peak), _p(silent), _p(cap_hops),
+                                   nthreads)
+        return lst, qf, bad, n, hops, done, peak, silent, cap_hops
 
 
 def infohash_get(keys):
