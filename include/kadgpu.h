@@ -625,6 +625,74 @@ int kad_sr_insert(kad_searches* ss, uint32_t m, const uint32_t* which, const uin
  * last kad_sr_insert on this set, in milliseconds (0 before the first). */
 int kad_sr_insert_kernel_ms(const kad_searches* ss, float* out_ms);
 
+/* ---- A whole tick of Dht::trySearchInsert on the device set (dht.cpp:816-849) ---- */
+/* One round's host plan, without a device (as kad_search_trim): the verdicts lb / fwd / back / stop of the r candidates
+ * that remain, in arrival order, plus trim[k]: bit 0 = the forward stopper refused as FAR or FAR_EXPIRED and holds
+ * entries past its trim position (full && t < n: the refusal still cuts its list), bit 1 = the same for the backward
+ * stopper. A candidate probes T = [lb-back-1, lb+fwd] without the ends whose stop is KAD_SR_STOP_END.
+ *   KAD_SR_PLAN_SKIPPED   fwd + back == 0, both stops END or FAR, neither stopper trims: final, nothing to apply
+ *   KAD_SR_PLAN_READY     T meets no T of an earlier candidate that was not skipped and does not lie on the open side of
+ *                         an earlier deferred one; its pairs may be applied now, in any order with the other ready ones
+ *   KAD_SR_PLAN_DEFERRED  everything else: it waits for the next round's verdicts. With a forward stop KNOWN or
+ *                         FAR_EXPIRED (stops an earlier insert can undo) it blocks every search from its lowest probed
+ *                         index upwards, with such a backward stop every search from its highest probed index downwards.
+ * out_kind: r bytes. The pairs of the ready candidates, ascending by search: out_pair_which (the search), out_pair_cand
+ * (the candidate's position k in the round) and out_pair_want (1 for an accepting search, 0 for a stopper that trims),
+ * room for S each; no two pairs share a search. KAD_ERR_INVALID: a NULL array that is needed, a stop code above 3, a
+ * verdict that reaches outside the S searches. */
+#define KAD_SR_PLAN_SKIPPED 0u
+#define KAD_SR_PLAN_READY 1u
+#define KAD_SR_PLAN_DEFERRED 2u
+int kad_sr_plan_round(uint32_t S, uint32_t r, const uint32_t* lb, const uint32_t* fwd, const uint32_t* back,
+                      const uint8_t* stop, const uint8_t* trim, uint8_t* out_kind, uint32_t* out_pair_which,
+                      uint32_t* out_pair_cand, uint8_t* out_pair_want, uint32_t* out_n_pairs);
+
+/* Dht::trySearchInsert of the q candidates cand_ids, in arrival order, applied to the device set in one call:
+ * cand_flags & KAD_SN_BAD = node->isExpired(), NULL = all zero. The candidate IDs are uploaded once. Then rounds: the
+ * verdict kernel over the candidates that remain (the walk of kad_sr_try_insert_batch plus the two trim bits read from
+ * the stoppers' records), the verdicts copied back, kad_sr_plan_round's plan, the pairs of the ready candidates uploaded
+ * as (search, candidate position), the candidates' IDs and BAD bits gathered on the device and kad_sr_insert's kernel
+ * run over them, one candidate per listed search, and the result bytes copied back. Nothing of size S crosses the bus.
+ * Every result byte is compared with the plan's expectation; a disagreement on a search that did not overflow ends the
+ * call with KAD_ERR_HIP, the rounds already applied staying described by the outputs.
+ *   out_kind[j]   KAD_SR_TICK_*; for SKIPPED and APPLIED candidates out_round[j] is the round (from 1) that decided it
+ *                 and out_lb / out_fwd / out_back / out_stop / out_trim[j] that round's verdict. For LEFT candidates
+ *                 these are unspecified.
+ *   replay        the host replays the APPLIED candidates on its own lists in (round, position) order: insertNode on
+ *                 [lb, lb+fwd] forwards and [lb-back-1, lb) backwards until the refusal the verdict names (a stopper
+ *                 whose trim bit is set is cut by it). Its searches then equal those of q sequential calls.
+ *   overflow      a pair whose search would outgrow its slab leaves that search untouched on the device
+ *                 (KAD_SR_INSERT_OVERFLOW); the search goes into out_overflow (ascending, distinct, room for S), its
+ *                 candidate stays APPLIED, the round is finished and the call stops: everything not decided yet is LEFT.
+ *                 The host replays as usual and patches the listed searches from its lists (kad_searches_patch, after
+ *                 kad_searches_apply with a larger cap where a list no longer fits).
+ * The call ends when no candidate remains, after max_rounds rounds (0: no limit) or after a round with an overflow. LEFT
+ * candidates may precede APPLIED ones; walking them on the host afterwards, in order, is exact, because a ready candidate
+ * never touches what an earlier waiting one can reach. Precondition, as for kad_sr_insert: the set's KAD_SN_REMOVABLE
+ * bits are those of the tick's `now`, and no candidate's own node is removable at `now` (such a candidate is a barrier:
+ * the caller cuts the tick there).
+ * Host arrays, synchronous; as kad_sr_insert towards queries (it first waits for all device work enqueued before the
+ * call). Checked in this order, before any device work, every failure leaving the set unchanged: NULL ss; NULL cand_ids
+ * or per-candidate output with q > 0; NULL out_overflow or out_n_overflow; a flag byte with bits other than KAD_SN_BAD
+ * (all KAD_ERR_INVALID); q == 0 or S == 0 (KAD_OK: every candidate SKIPPED in round 0 with lb = fwd = back = stop =
+ * trim = 0, no device work); cap > 64 (KAD_ERR_UNSUPPORTED). Out of host or device memory: KAD_ERR_NOMEM. The device
+ * scratch is one allocation per call. out_stats (may be NULL): the rounds run, the candidates by kind, the pairs
+ * applied, the searches that overflowed, and the device time of the verdict kernels and of the gather and insert kernels,
+ * summed over the rounds. */
+#define KAD_SR_TICK_LEFT 0u      /* not handled: ask again or walk it on the host */
+#define KAD_SR_TICK_SKIPPED 1u   /* refused as too far by both neighbours, nothing trimmed: final */
+#define KAD_SR_TICK_APPLIED 2u   /* its verdict was applied to the device set in round out_round[j] */
+typedef struct {
+    uint32_t rounds, skipped, applied, left, pairs, overflowed;
+    float verdict_ms, insert_ms;
+} kad_sr_tick_stats;
+int kad_sr_try_insert_tick(kad_searches* ss, const uint8_t* cand_ids, const uint8_t* cand_flags, uint32_t q,
+                           uint32_t max_rounds /* 0: no limit */,
+                           uint8_t* out_kind, uint32_t* out_round, uint32_t* out_lb, uint32_t* out_fwd,
+                           uint32_t* out_back, uint8_t* out_stop, uint8_t* out_trim,
+                           uint32_t* out_overflow /* room for S */, uint32_t* out_n_overflow,
+                           kad_sr_tick_stats* out_stats /* may be NULL */);
+
 /* ---- Node status changes over a set of live searches (SearchNode::isBad dht.cpp:458-460, Node::setExpired) ---- */
 /* The reference keeps no flag byte: isBad() reads the shared Node, so one setExpired() after a timed-out request, one
  * reply (expired_ = false) or ten minutes passing for an expired node changes KAD_SN_BAD / KAD_SN_REMOVABLE in every

@@ -838,6 +838,29 @@ struct InsertResult {
     bool overflow;
 };
 
+/* One candidate of SearchesMirror::trySearchInsertTick (kad_sr_try_insert_tick): kind is KAD_SR_TICK_LEFT, _SKIPPED or
+ * _APPLIED; for the last two, round is the round that decided it and lb / fwd / back / stop / trim that round's verdict:
+ * the searches [lb - back, lb + fwd) in map order took the candidate, stop = fstop | bstop << 4 (KAD_SR_STOP_*) says why
+ * each walk ended, and trim bit 0 / bit 1 says that the forward / backward stopper's refusal cut its list. lb_id is the
+ * ID of search lb (the map's lower_bound of the node's ID), at_end is set when lb is past the last search. */
+template <class InfoHashT>
+struct TickVerdict {
+    uint8_t kind;
+    uint32_t round, lb, fwd, back;
+    uint8_t stop, trim;
+    bool at_end;
+    InfoHashT lb_id;
+};
+
+/* A tick of SearchesMirror::trySearchInsertTick: one verdict per candidate, and the searches the device left untouched
+ * because their slab is too small (their candidates stay APPLIED; the host's replay stands and the searches are reported
+ * to sync(changed, now)). */
+template <class InfoHashT>
+struct TickResult {
+    std::vector<TickVerdict<InfoHashT>> verdicts;
+    std::vector<InfoHashT> overflowed;
+};
+
 /* One search whose flag bytes SearchesMirror::markNodes changed, with the counts of its list after the change: n,
  * Search::getNumberOfBadNodes(), getNumberOfConsecutiveBadNodes() (dht.cpp:583-597), and whether it is full (at least
  * SEARCH_NODES entries that are not bad) and expired. Dht::searchStep's expiry test is lead_bad >= min(n,
@@ -1073,6 +1096,77 @@ public:
             if (!r.overflow) r.inserted.assign(ins.begin() + off[k], ins.begin() + off[k + 1]);
             at_[which[k]] = when.ns();
         }
+        return out;
+    }
+
+    /* Dht::trySearchInsert(n) for every node n of `nodes`, in arrival order, applied to the device set in one call
+     * (kad_sr_try_insert_tick, up to max_rounds rounds, 0: no limit), KAD_SN_BAD = n->isExpired(). The candidates go up
+     * to the first one whose node is removable at `now`: insertNode's node.time = now clears that node's REMOVABLE bit in
+     * every search that holds it, so that candidate is the caller's to walk on the host, and it and all after it come
+     * back as KAD_SR_TICK_LEFT. As insertBatch, the searches whose KAD_SN_REMOVABLE bits at `now` differ from the
+     * mirrored ones are patched first (same precondition); here that is asked of every mirrored search, since a tick may
+     * reach any of them. The host then replays the APPLIED candidates on its own searches in (round, position) order:
+     * insertNode from search lb forwards and from lb - 1 backwards until the first refusal, which the verdict names (a
+     * refusing search whose trim bit is set is cut by that call). Then it walks the LEFT candidates in order, as
+     * Dht::trySearchInsert does, and reports the searches those walks changed, every search holding a removable
+     * candidate that was accepted, and `overflowed` to sync(changed, now). */
+    template <class NodePtrT, class TimePoint, class MapT = SearchMapT, class InfoHashT = typename MapT::key_type>
+    TickResult<InfoHashT> trySearchInsertTick(const std::vector<NodePtrT>& nodes, TimePoint now, uint32_t max_rounds = 0) {
+        TickResult<InfoHashT> out;
+        if (nodes.empty()) return out;
+        if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::trySearchInsertTick before snapshot");
+        const At<TimePoint> when{now};
+        TickVerdict<InfoHashT> left = TickVerdict<InfoHashT>();
+        left.kind = (uint8_t)KAD_SR_TICK_LEFT;
+        out.verdicts.assign(nodes.size(), left);
+        size_t cut = 0;
+        while (cut < nodes.size() && !when.removable(*nodes[cut])) cut++;
+        // every search's key, and the searches whose REMOVABLE bits moved since they were uploaded
+        std::vector<const InfoHashT*> keys;
+        std::vector<InfoHashT> moved;
+        keys.reserve(size());
+        for (const auto& kv : *map_) {
+            const size_t at = keys.size();
+            if (at >= size() || std::memcmp(id_bytes(kv.first), &ids_[at * KAD_HASH_LEN], KAD_HASH_LEN) != 0)
+                throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
+            bool differ = false;
+            for (const auto& sn : kv.second->nodes)
+                differ = differ || when.removable(*sn.node) != (at_[at] != INT64_MIN && when.removableAt(*sn.node, at_[at]));
+            if (differ) moved.push_back(kv.first);
+            keys.push_back(&kv.first);
+        }
+        if (keys.size() != size()) throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
+        if (cut == 0) return out;
+        if (!moved.empty()) syncAt(moved, when);
+        const uint32_t q = (uint32_t)cut;
+        std::vector<uint8_t> cid((size_t)q * KAD_HASH_LEN), cfl(q), kind(q), stop(q), trim(q);
+        std::vector<uint32_t> round(q), lb(q), fwd(q), back(q), over(size() + 1);
+        for (uint32_t j = 0; j < q; j++) {
+            std::memcpy(&cid[(size_t)j * KAD_HASH_LEN], id_bytes(nodes[j]->id), KAD_HASH_LEN);
+            cfl[j] = nodes[j]->isExpired() ? (uint8_t)KAD_SN_BAD : (uint8_t)0;
+        }
+        uint32_t n_over = 0;
+        const int rc = kad_sr_try_insert_tick(ss_, cid.data(), cfl.data(), q, max_rounds, kind.data(), round.data(),
+                                              lb.data(), fwd.data(), back.data(), stop.data(), trim.data(), over.data(),
+                                              &n_over, nullptr);
+        // every mirrored search now carries the bits of `now`: the moved ones were patched, the others do not differ
+        // (whatever rounds an error left applied, the bits stay those of `now`)
+        for (auto& t : at_) t = when.ns();
+        check(rc, "kad_sr_try_insert_tick");
+        for (uint32_t j = 0; j < q; j++) {
+            TickVerdict<InfoHashT>& v = out.verdicts[j];
+            v.kind = kind[j];
+            if (kind[j] == KAD_SR_TICK_LEFT) continue;
+            v.round = round[j];
+            v.lb = lb[j];
+            v.fwd = fwd[j];
+            v.back = back[j];
+            v.stop = stop[j];
+            v.trim = trim[j];
+            v.at_end = lb[j] >= keys.size();
+            if (!v.at_end) v.lb_id = *keys[lb[j]];
+        }
+        for (uint32_t k = 0; k < n_over; k++) out.overflowed.push_back(*keys[over[k]]);
         return out;
     }
 
@@ -1399,6 +1493,13 @@ public:
     std::vector<InsertResult> insertBatch(sa_family_t af, const std::vector<InfoHashT>& ids,
                                           const std::vector<std::vector<NodePtrT>>& nodes) {
         return searches(af).insertBatch(ids, nodes, clock_());
+    }
+    /* Dht::trySearchInsert of the nodes of one tick on the searches of one family, applied on the device, at the
+     * mirror's clock (SearchesMirror::trySearchInsertTick); the host replays, and syncSearches(af, changed, now) reports
+     * the overflowed searches and what the walks of the LEFT candidates changed. */
+    template <class NodePtrT, class MapT = SearchMapT, class InfoHashT = typename MapT::key_type>
+    TickResult<InfoHashT> trySearchInsertTick(sa_family_t af, const std::vector<NodePtrT>& nodes, uint32_t max_rounds = 0) {
+        return searches(af).trySearchInsertTick(nodes, clock_(), max_rounds);
     }
     /* The node status changes of one tick for the searches of one family, at the mirror's clock
      * (SearchesMirror::markNodes). */

@@ -16,10 +16,12 @@ from ._lib import (KAD_SN_BAD, KAD_SR_EXPIRED, KAD_SR_STOP_END, KAD_SR_STOP_FAR,
 from ._lib import KAD_SN_REMOVABLE, KAD_SR_REFILL_OK, KAD_SR_REFILL_OVERFLOW
 from ._lib import KAD_SR_INSERT_OK, KAD_SR_INSERT_OVERFLOW
 from ._lib import KAD_SR_MARK_MAX_NODES
+from ._lib import (KAD_SR_PLAN_DEFERRED, KAD_SR_PLAN_READY, KAD_SR_PLAN_SKIPPED, KAD_SR_TICK_APPLIED, KAD_SR_TICK_LEFT,
+                   KAD_SR_TICK_SKIPPED)
 from ._lib import KAD_SWEEP_INCOMING
 from .ingest import ingest
-from .searches import (DeviceSearches, expire_searches, mark_search_nodes, plan_insert_round, refill_searches,
-                       start_searches, try_search_insert, try_search_insert_device)
+from .searches import (DeviceSearches, expire_searches, mark_search_nodes, plan_insert_round, plan_round, refill_searches,
+                       start_searches, try_search_insert, try_search_insert_device, try_search_insert_tick)
 from .table import DeviceTable, nc_closest_dual, rt_closest_dual, rt_responsible_dual
 
 __all__ = [
@@ -34,4 +36,6 @@ __all__ = [
     "start_searches", "expire_searches",
     "KAD_SR_INSERT_OK", "KAD_SR_INSERT_OVERFLOW", "plan_insert_round", "try_search_insert_device",
     "KAD_SR_MARK_MAX_NODES", "mark_search_nodes",
+    "KAD_SR_PLAN_DEFERRED", "KAD_SR_PLAN_READY", "KAD_SR_PLAN_SKIPPED", "KAD_SR_TICK_APPLIED", "KAD_SR_TICK_LEFT",
+    "KAD_SR_TICK_SKIPPED", "plan_round", "try_search_insert_tick",
 ]

@@ -43,6 +43,8 @@ KAD_SN_REMOVABLE = 0x02
 KAD_SR_REFILL_OK, KAD_SR_REFILL_OVERFLOW = 0, 1
 KAD_SR_INSERT_OK, KAD_SR_INSERT_OVERFLOW = 0, 1
 KAD_SR_MARK_MAX_NODES = 1 << 20
+KAD_SR_PLAN_SKIPPED, KAD_SR_PLAN_READY, KAD_SR_PLAN_DEFERRED = 0, 1, 2
+KAD_SR_TICK_LEFT, KAD_SR_TICK_SKIPPED, KAD_SR_TICK_APPLIED = 0, 1, 2
 KAD_SR_STOP_END, KAD_SR_STOP_KNOWN, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED = 0, 1, 2, 3
 KAD_SWEEP_INCOMING = 1
 
@@ -158,6 +160,8 @@ SIGNATURES = {
     "kad_sr_refill_kernel_ms": (C.c_int, [_P, _P]),
     "kad_sr_insert": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "kad_sr_insert_kernel_ms": (C.c_int, [_P, _P]),
+    "kad_sr_plan_round": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "kad_sr_try_insert_tick": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "kad_sr_mark_nodes": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "kad_sr_mark_kernel_ms": (C.c_int, [_P, _P, _P]),
     "kad_rt_shard_batch": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -262,6 +266,12 @@ class sweep_totals(C.Structure):
     """kad_sweep_totals"""
     _fields_ = [(n, C.c_uint32) for n in ("good", "dubious", "expired", "incoming", "changed_buckets", "empty_buckets",
                                           "flags", "reserved")]
+
+
+class sr_tick_stats(C.Structure):
+    """kad_sr_tick_stats"""
+    _fields_ = [(n, C.c_uint32) for n in ("rounds", "skipped", "applied", "left", "pairs", "overflowed")] + [
+        ("verdict_ms", C.c_float), ("insert_ms", C.c_float)]
 
 
 class refresh_diag(C.Structure):

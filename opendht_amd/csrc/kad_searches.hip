@@ -25,6 +25,11 @@
 // each with its own KAD_SN_BAD bit, applied in place by insert_kernel in the same one-wave-per-search form: the accepted
 // inserts of a trySearchInsert tick without an upload of the touched lists.
 //
+// kad_sr_try_insert_tick is a whole tick of trySearchInsert in one call: the candidates stay resident in
+// the call's scratch, tick_verdict_kernel gives the verdicts of the candidates that remain plus the stoppers' trim bits,
+// the host plans the round (kadplan::sr_round_plan), tick_gather_kernel lays the ready pairs' candidates out as the CSR
+// insert_kernel reads, and insert_kernel applies them; round after round until nothing waits.
+//
 // kad_sr_mark_nodes carries node status changes (Node::setExpired, a reply, the candidate bit) to the
 // flag bytes of every list that holds the node: mark_scan_kernel streams the member keys against the tick's sorted batch
 // of node IDs, mark_pairs_kernel sets single (search, node) entries, mark_fix_kernel derives the changed searches'
@@ -38,6 +43,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <new>
 #include <numeric>
@@ -51,7 +57,7 @@
 // tests/test_refill_abi.py, test_searches_abi.py and test_searches_apply_abi.py hand the argument checks a zeroed
 // buffer for a set: it must read as a set of no searches (S == 0, cap == 0, no pointer followed before the checks end,
 // rf_ms == 0); tests/test_sr_insert_abi.py does the same (in_ms == 0), and tests/test_sr_mark_abi.py (no mark scratch,
-// mk_ms == 0).
+// mk_ms == 0) and tests/test_sr_tick_abi.py (S == 0 answers before anything else of the set is read).
 struct kad_searches {
     int device = 0;
     uint32_t S = 0, cap = 0;
@@ -75,6 +81,8 @@ struct kad_searches {
     uint64_t mk_bytes = 0;
     hipEvent_t mk_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the last call's scan and fix kernels
     float mk_ms[2] = {0.f, 0.f};
+    // around a kad_sr_try_insert_tick round's verdict kernel, and around its gather and insert kernels
+    hipEvent_t tk_ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 namespace {
@@ -285,6 +293,78 @@ int launch(const kad_searches* ss, const uint8_t* ids, uint32_t q, uint32_t* out
                            out_back, out_stop);
     SR_HIP_TRY(hipGetLastError());
     return KAD_OK;
+}
+
+// ---- kad_sr_try_insert_tick's verdicts ------------------------------------------------------------
+// try_insert_kernel's walk over a subset of the candidates resident in the call's scratch: lane i takes candidate
+// rem[i] (NULL: candidate i, the first round). A FAR / FAR_EXPIRED refusal also reads, from the stopper's record the
+// walk holds in registers, whether the refusal cuts that search's list (full and t < n): the round's plan needs nothing
+// else about the searches. One 16-byte store per candidate: {lb, fwd, back, fstop | bstop << 4 | trim << 8}.
+__device__ __forceinline__ uint32_t refusal_trims(const Rec& R, uint32_t v) {
+    return (v == KAD_SR_STOP_FAR || v == KAD_SR_STOP_FAR_EXPIRED) && (R.r3.x & SREC_FULL) && R.r2.w < R.r1.y ? 1u : 0u;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(BLOCK) void tick_verdict_kernel(DevSearches D, const uint8_t* __restrict__ ids,
+                                                             const uint32_t* __restrict__ rem, uint32_t r,
+                                                             u32x4_t* __restrict__ out) {
+    __shared__ uint64_t sk[LDS ? LDS_KEYS : 1];
+    if (LDS) {
+        for (uint32_t j = threadIdx.x; j < D.S; j += BLOCK) sk[j] = D.skey[j];
+        __syncthreads();
+    }
+    for (uint64_t i0 = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i0 < r; i0 += (uint64_t)gridDim.x * BLOCK) {
+        const uint32_t i = (uint32_t)i0;
+        const Cand x = load_cand(ids, rem ? rem[i] : i);
+        // lower_bound over the 160-bit search IDs, as try_insert_kernel (D.S > 0 here)
+        uint32_t lo = 0, hi = D.S;
+        if (!LDS) {
+            const uint32_t p = (uint32_t)(x.hi >> D.rshift);
+            lo = D.rdx[p];
+            hi = D.rdx[p + 1];
+        }
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            const u32x4_t* rr = D.rec + 4ull * mid;
+            u32x4_t r0 = {};
+            if (!LDS) r0 = rr[0];
+            const uint64_t k = LDS ? sk[mid] : (((uint64_t)r0.y << 32) | r0.x);
+            bool less = k < x.hi;
+            if (k == x.hi) {
+                if (LDS) r0 = rr[0];
+                less = tail_less(r0.z, r0.w, rr[1].x, x.t2, x.t3, x.t4);
+            }
+            if (less)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        const uint32_t lb = lo;
+        uint32_t fwd = 0, back = 0, fstop = KAD_SR_STOP_END, bstop = KAD_SR_STOP_END, trim = 0;
+        Rec rf = load_rec(D, min(lb, D.S - 1u)), rb = load_rec(D, max(lb, 1u) - 1u);
+        for (uint32_t s = lb; s < D.S;) {  // insert forward (dht.cpp:826-836)
+            const uint32_t v = probe(D, s, rf, x);
+            if (v != ACCEPT) {
+                fstop = v;
+                trim = refusal_trims(rf, v);
+                break;
+            }
+            fwd++;
+            if (++s < D.S) rf = load_rec(D, s);
+        }
+        for (uint32_t s = lb; s > 0;) {  // insert backward (dht.cpp:837-847)
+            const uint32_t v = probe(D, --s, rb, x);
+            if (v != ACCEPT) {
+                bstop = v;
+                trim |= refusal_trims(rb, v) << 1;
+                break;
+            }
+            back++;
+            if (s > 0) rb = load_rec(D, s - 1u);
+        }
+        const u32x4_t v = {lb, fwd, back, fstop | (bstop << 4) | (trim << 8)};
+        __builtin_nontemporal_store(v, out + i);
+    }
 }
 
 // ---- kad_sr_refill: Dht::refill over the set ------------------------------------------------------
@@ -660,6 +740,29 @@ __global__ __launch_bounds__(BLOCK) void insert_kernel(DevInsert D) {
         }
     }
     if (lane == 0) D.out_status[i] = overflow ? (uint8_t)KAD_SR_INSERT_OVERFLOW : (uint8_t)KAD_SR_INSERT_OK;
+}
+
+// kad_sr_try_insert_tick's round inserts: the pairs of a round never share a search, so pair i is the
+// one candidate of its search. Its ID and BAD bit are gathered by position from the candidates resident in the call's
+// scratch into the CSR insert_kernel reads (off[i] = i), and insert_kernel runs unmodified over it.
+__global__ __launch_bounds__(BLOCK) void tick_gather_kernel(const uint8_t* __restrict__ ids,
+                                                            const uint8_t* __restrict__ flags,
+                                                            const uint32_t* __restrict__ pos, uint32_t m,
+                                                            uint32_t* __restrict__ off, uint32_t* __restrict__ gids,
+                                                            uint8_t* __restrict__ gflags) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i > m) return;
+    off[i] = i;  // m + 1 offsets
+    if (i == m) return;
+    const uint32_t j = pos[i];
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(ids + 20ull * j);
+    uint32_t* g = gids + 5ull * i;
+    g[0] = p[0];
+    g[1] = p[1];
+    g[2] = p[2];
+    g[3] = p[3];
+    g[4] = p[4];
+    gflags[i] = flags[j];
 }
 
 // ---- kad_sr_mark_nodes: node status changes over the set -----------------------------------------
@@ -1312,9 +1415,11 @@ int kad_searches_export(const kad_searches* ss, uint8_t* ids, uint8_t* flags, ui
 
 int kad_searches_destroy(kad_searches* ss) {
     if (!ss) return KAD_OK;
-    if (ss->S || ss->rf_ev[0] || ss->in_ev[0] || ss->mk_ev[0] || ss->mk_buf) {  // apply can empty a set that holds events
+    if (ss->S || ss->rf_ev[0] || ss->in_ev[0] || ss->mk_ev[0] || ss->mk_buf || ss->tk_ev[0]) {  // apply can empty a set that holds events
         DeviceGuard g(ss->device);
         (void)hipDeviceSynchronize();
+        for (hipEvent_t e : ss->tk_ev)
+            if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ss->rf_ev)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ss->in_ev)
@@ -1477,6 +1582,194 @@ int kad_sr_insert_kernel_ms(const kad_searches* ss, float* out_ms) {
     if (!ss || !out_ms) return set_error(KAD_ERR_INVALID, "NULL argument");
     *out_ms = ss->in_ms;
     return KAD_OK;
+}
+
+int kad_sr_try_insert_tick(kad_searches* ss, const uint8_t* cand_ids, const uint8_t* cand_flags, uint32_t q,
+                           uint32_t max_rounds, uint8_t* out_kind, uint32_t* out_round, uint32_t* out_lb,
+                           uint32_t* out_fwd, uint32_t* out_back, uint8_t* out_stop, uint8_t* out_trim,
+                           uint32_t* out_overflow, uint32_t* out_n_overflow, kad_sr_tick_stats* out_stats) {
+    if (!ss) return set_error(KAD_ERR_INVALID, "NULL search set");
+    if (q && (!cand_ids || !out_kind || !out_round || !out_lb || !out_fwd || !out_back || !out_stop || !out_trim))
+        return set_error(KAD_ERR_INVALID, "NULL candidate or output array");
+    if (!out_overflow || !out_n_overflow) return set_error(KAD_ERR_INVALID, "NULL overflow outputs");
+    for (uint32_t j = 0; cand_flags && j < q; j++)
+        if (cand_flags[j] & ~KAD_SN_BAD) return set_error(KAD_ERR_INVALID, "candidate flags: only KAD_SN_BAD may be set");
+    kad_sr_tick_stats st = {};
+    *out_n_overflow = 0;
+    if (q == 0 || ss->S == 0) {  // no search refuses, none accepts
+        for (uint32_t j = 0; j < q; j++) {
+            out_kind[j] = (uint8_t)KAD_SR_TICK_SKIPPED;
+            out_round[j] = out_lb[j] = out_fwd[j] = out_back[j] = 0;
+            out_stop[j] = out_trim[j] = 0;
+        }
+        st.skipped = q;
+        if (out_stats) *out_stats = st;
+        return KAD_OK;
+    }
+    if (ss->cap > REFILL_MAX_CAP)
+        return set_error(KAD_ERR_UNSUPPORTED, "kad_sr_try_insert_tick handles slabs of up to 64 entries");
+    const uint32_t S = ss->S;
+    // a round's pairs never share a search: at most S, sent in slices of P
+    const uint64_t want_p = 2ull * q + 1024;
+    const uint32_t P = (uint32_t)(want_p < S ? want_p : S);
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    // the call's scratch, one allocation: the candidates' IDs and flags (uploaded once), the positions that remain, the
+    // verdicts, then per slice of pairs the searches and positions (one upload), the CSR insert_kernel reads and the
+    // result and status bytes (one copy back)
+    const size_t o_fl = up16(20ull * q), o_rem = up16(o_fl + q), o_ver = up16(o_rem + 4ull * q), o_pw = o_ver + 16ull * q,
+                 o_off = up16(o_pw + 8ull * P), o_gid = up16(o_off + 4ull * (P + 1)), o_gfl = up16(o_gid + 20ull * P),
+                 o_ins = up16(o_gfl + P), total = o_ins + 2ull * P;
+    std::vector<uint32_t> h_ver, lb, fwd, back, rem, h_pairs;
+    std::vector<uint8_t> stop, trim, h_res;
+    kadplan::SrRoundPlan plan;
+    try {
+        h_ver.resize(4ull * q);
+        lb.resize(q);
+        fwd.resize(q);
+        back.resize(q);
+        stop.resize(q);
+        trim.resize(q);
+        rem.resize(q);
+        h_pairs.resize(2ull * P);
+        h_res.resize(2ull * P);
+        plan.kind.reserve(q);
+        plan.marked.reserve(((size_t)S + 63) / 64 + 1);
+    } catch (const std::bad_alloc&) {
+        return set_error(KAD_ERR_NOMEM, "tick: out of host memory");
+    }
+    DeviceGuard g(ss->device);
+    uint8_t* buf = nullptr;
+    uint32_t n_rem = q, n_over = 0;
+    auto done = [&](int r) {
+        if (buf) (void)hipFree(buf);
+        st.left = n_rem;
+        st.overflowed = n_over;
+        *out_n_overflow = n_over;
+        if (out_stats) *out_stats = st;
+        return r;
+    };
+    std::memset(out_kind, (int)KAD_SR_TICK_LEFT, q);
+    if (hipDeviceSynchronize() != hipSuccess)  // queries enqueued before the call read the old set
+        return done(set_error(KAD_ERR_HIP, "tick: device in error"));
+    if (hipMalloc((void**)&buf, total) != hipSuccess) {
+        (void)hipGetLastError();
+        buf = nullptr;
+        return done(set_error(KAD_ERR_NOMEM, "tick: out of device memory"));
+    }
+    for (hipEvent_t& e : ss->tk_ev)
+        if (!e && hipEventCreate(&e) != hipSuccess) return done(set_error(KAD_ERR_HIP, "tick: no events"));
+    if (hipMemcpy(buf, cand_ids, 20ull * q, hipMemcpyHostToDevice) != hipSuccess ||
+        (cand_flags ? hipMemcpy(buf + o_fl, cand_flags, q, hipMemcpyHostToDevice)
+                    : hipMemset(buf + o_fl, 0, q)) != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, "tick: H2D failed"));
+    const DevSearches V{reinterpret_cast<const u32x4_t*>(ss->rec), ss->skey, ss->mkey, ss->mtail, ss->rdx, S, ss->cap,
+                        ss->rshift};
+    uint32_t* d_rem = (uint32_t*)(buf + o_rem);
+    uint32_t* d_pw = (uint32_t*)(buf + o_pw);
+    for (uint32_t j = 0; j < q; j++) rem[j] = j;
+    std::string err;
+    while (n_rem && n_over == 0 && (max_rounds == 0 || st.rounds < max_rounds)) {
+        const uint32_t r = n_rem, round = ++st.rounds;
+        if (round > 1 && hipMemcpy(d_rem, rem.data(), 4ull * r, hipMemcpyHostToDevice) != hipSuccess)
+            return done(set_error(KAD_ERR_HIP, "tick: H2D of the remaining candidates failed"));
+        const uint32_t blocks = (r + BLOCK - 1) / BLOCK, grid = blocks < MAX_GRID ? blocks : MAX_GRID;
+        (void)hipEventRecord(ss->tk_ev[0], nullptr);
+        if (S <= LDS_KEYS)
+            hipLaunchKernelGGL(tick_verdict_kernel<true>, dim3(grid), dim3(BLOCK), 0, nullptr, V, buf,
+                               round > 1 ? d_rem : nullptr, r, (u32x4_t*)(buf + o_ver));
+        else
+            hipLaunchKernelGGL(tick_verdict_kernel<false>, dim3(grid), dim3(BLOCK), 0, nullptr, V, buf,
+                               round > 1 ? d_rem : nullptr, r, (u32x4_t*)(buf + o_ver));
+        hipError_t le = hipGetLastError();
+        (void)hipEventRecord(ss->tk_ev[1], nullptr);
+        if (le != hipSuccess)
+            return done(set_error(KAD_ERR_HIP, (std::string("tick: verdict launch failed: ") + hipGetErrorString(le)).c_str()));
+        le = hipMemcpy(h_ver.data(), buf + o_ver, 16ull * r, hipMemcpyDeviceToHost);
+        if (le != hipSuccess)
+            return done(set_error(KAD_ERR_HIP, (std::string("tick: D2H of the verdicts failed: ") + hipGetErrorString(le)).c_str()));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ss->tk_ev[0], ss->tk_ev[1]) == hipSuccess)
+            st.verdict_ms += ms;
+        else
+            (void)hipGetLastError();
+        for (uint32_t k = 0; k < r; k++) {
+            lb[k] = h_ver[4ull * k];
+            fwd[k] = h_ver[4ull * k + 1];
+            back[k] = h_ver[4ull * k + 2];
+            stop[k] = (uint8_t)h_ver[4ull * k + 3];
+            trim[k] = (uint8_t)((h_ver[4ull * k + 3] >> 8) & 3u);
+        }
+        try {
+            if (kadplan::sr_round_plan(S, r, lb.data(), fwd.data(), back.data(), stop.data(), trim.data(), plan, err))
+                return done(set_error(KAD_ERR_HIP, ("tick: verdict out of range: " + err).c_str()));
+        } catch (const std::bad_alloc&) {
+            return done(set_error(KAD_ERR_NOMEM, "tick: out of host memory"));
+        }
+        // the round's outputs stand before its inserts run: whatever happens then, they describe what was applied
+        uint32_t n_next = 0;
+        for (uint32_t k = 0; k < r; k++) {
+            const uint32_t j = rem[k];
+            if (plan.kind[k] == kadplan::SR_PLAN_DEFERRED) {
+                n_next++;
+                continue;
+            }
+            const bool ready = plan.kind[k] == kadplan::SR_PLAN_READY;
+            out_kind[j] = ready ? (uint8_t)KAD_SR_TICK_APPLIED : (uint8_t)KAD_SR_TICK_SKIPPED;
+            out_round[j] = round;
+            out_lb[j] = lb[k];
+            out_fwd[j] = fwd[k];
+            out_back[j] = back[k];
+            out_stop[j] = stop[k];
+            out_trim[j] = trim[k];
+            (ready ? st.applied : st.skipped)++;
+        }
+        n_rem = n_next;  // what waits for the next round, or stays LEFT
+        const size_t n_pairs = plan.pair_which.size();
+        for (size_t a = 0; a < n_pairs; a += P) {
+            const uint32_t m = (uint32_t)(n_pairs - a < P ? n_pairs - a : P);
+            for (uint32_t i = 0; i < m; i++) {
+                h_pairs[i] = plan.pair_which[a + i];
+                h_pairs[m + i] = rem[plan.pair_cand[a + i]];
+            }
+            if (hipMemcpy(d_pw, h_pairs.data(), 8ull * m, hipMemcpyHostToDevice) != hipSuccess)
+                return done(set_error(KAD_ERR_HIP, "tick: H2D of the pairs failed"));
+            const DevInsert D{ss->rec, ss->mkey, ss->mtail, ss->mflag, ss->cap, m, d_pw, (const uint32_t*)(buf + o_off),
+                              buf + o_gid, buf + o_gfl, buf + o_ins, buf + o_ins + m};
+            (void)hipEventRecord(ss->tk_ev[2], nullptr);
+            hipLaunchKernelGGL(tick_gather_kernel, dim3(m / BLOCK + 1), dim3(BLOCK), 0, nullptr, buf, buf + o_fl, d_pw + m,
+                               m, (uint32_t*)(buf + o_off), (uint32_t*)(buf + o_gid), buf + o_gfl);
+            le = hipGetLastError();
+            if (le == hipSuccess) {
+                hipLaunchKernelGGL(insert_kernel, dim3((m + REFILL_WAVES - 1) / REFILL_WAVES), dim3(BLOCK), 0, nullptr, D);
+                le = hipGetLastError();
+            }
+            (void)hipEventRecord(ss->tk_ev[3], nullptr);
+            if (le != hipSuccess)
+                return done(set_error(KAD_ERR_HIP, (std::string("tick: insert launch failed: ") + hipGetErrorString(le)).c_str()));
+            le = hipMemcpy(h_res.data(), buf + o_ins, 2ull * m, hipMemcpyDeviceToHost);
+            if (le != hipSuccess)
+                return done(set_error(KAD_ERR_HIP, (std::string("tick: D2H of the results failed: ") + hipGetErrorString(le)).c_str()));
+            if (hipEventElapsedTime(&ms, ss->tk_ev[2], ss->tk_ev[3]) == hipSuccess)
+                st.insert_ms += ms;
+            else
+                (void)hipGetLastError();
+            st.pairs += m;
+            for (uint32_t i = 0; i < m; i++) {
+                if (h_res[m + i] == KAD_SR_INSERT_OVERFLOW) {
+                    out_overflow[n_over++] = plan.pair_which[a + i];  // the pairs ascend by search
+                } else if (h_res[i] != plan.pair_want[a + i]) {
+                    char msg[160];
+                    std::snprintf(msg, sizeof msg, "tick: round %u, search %u answered %u to candidate %u against its verdict",
+                                  round, plan.pair_which[a + i], (unsigned)h_res[i], rem[plan.pair_cand[a + i]]);
+                    return done(set_error(KAD_ERR_HIP, msg));
+                }
+            }
+        }
+        n_next = 0;
+        for (uint32_t k = 0; k < r; k++)
+            if (plan.kind[k] == kadplan::SR_PLAN_DEFERRED) rem[n_next++] = rem[k];
+    }
+    return done(KAD_OK);
 }
 
 int kad_sr_mark_nodes(kad_searches* ss, uint32_t q, const uint8_t* node_ids, const uint8_t* clear_bits,

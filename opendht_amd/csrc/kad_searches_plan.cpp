@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <new>
 
 #include "../../include/kadgpu.h"
 
@@ -176,6 +177,93 @@ int sr_insert_check(uint32_t S, uint32_t m, const uint32_t* which, const uint32_
     return KAD_OK;
 }
 
+namespace {
+
+// bits lo .. hi (inclusive) of the bitmap, a word at a time
+bool any_marked(const uint64_t* w, uint32_t lo, uint32_t hi) {
+    const uint32_t a = lo >> 6, b = hi >> 6;
+    const uint64_t first = ~0ull << (lo & 63u), last = ~0ull >> (63u - (hi & 63u));
+    if (a == b) return (w[a] & first & last) != 0;
+    if (w[a] & first) return true;
+    for (uint32_t i = a + 1; i < b; i++)
+        if (w[i]) return true;
+    return (w[b] & last) != 0;
+}
+
+void mark(uint64_t* w, uint32_t lo, uint32_t hi) {
+    const uint32_t a = lo >> 6, b = hi >> 6;
+    const uint64_t first = ~0ull << (lo & 63u), last = ~0ull >> (63u - (hi & 63u));
+    if (a == b) {
+        w[a] |= first & last;
+        return;
+    }
+    w[a] |= first;
+    for (uint32_t i = a + 1; i < b; i++) w[i] = ~0ull;
+    w[b] |= last;
+}
+
+}  // namespace
+
+int sr_round_plan(uint32_t S, uint32_t r, const uint32_t* lb, const uint32_t* fwd, const uint32_t* back,
+                  const uint8_t* stop, const uint8_t* trim, SrRoundPlan& out, std::string& err) {
+    for (uint32_t k = 0; k < r; k++) {
+        const uint32_t fs = stop[k] & 15u, bs = stop[k] >> 4;
+        if (fs > KAD_SR_STOP_FAR_EXPIRED || bs > KAD_SR_STOP_FAR_EXPIRED)
+            return fail(err, KAD_ERR_INVALID, "candidate %u: unknown stop code", k);
+        if (lb[k] > S || fwd[k] > S - lb[k] || back[k] > lb[k])
+            return fail(err, KAD_ERR_INVALID, "candidate %u: verdict outside the %u searches", k, S);
+        if ((fs != KAD_SR_STOP_END && lb[k] + fwd[k] >= S) || (bs != KAD_SR_STOP_END && back[k] >= lb[k]))
+            return fail(err, KAD_ERR_INVALID, "candidate %u: a stop without a search that refused", k);
+    }
+    out.kind.assign(r, SR_PLAN_SKIPPED);
+    out.pair_which.clear();
+    out.pair_cand.clear();
+    out.pair_want.clear();
+    out.ready.clear();
+    out.marked.assign(((size_t)S + 63) / 64 + 1, 0ull);
+    uint64_t* marked = out.marked.data();
+    int64_t block_up = S, block_down = -1;  // searches >= block_up and <= block_down are blocked
+    auto is_far = [](uint32_t v) { return v == KAD_SR_STOP_FAR || v == KAD_SR_STOP_FAR_EXPIRED; };
+    auto is_open = [](uint32_t v) { return v == KAD_SR_STOP_KNOWN || v == KAD_SR_STOP_FAR_EXPIRED; };
+    auto final_stop = [](uint32_t v) { return v == KAD_SR_STOP_END || v == KAD_SR_STOP_FAR; };
+    for (uint32_t k = 0; k < r; k++) {
+        const uint32_t fs = stop[k] & 15u, bs = stop[k] >> 4;
+        const bool ftrim = is_far(fs) && (trim[k] & 1u), btrim = is_far(bs) && (trim[k] & 2u);
+        if (fwd[k] + back[k] == 0 && final_stop(fs) && final_stop(bs) && !ftrim && !btrim) continue;
+        const int64_t lo = (int64_t)lb[k] - back[k] - (bs == KAD_SR_STOP_END ? 0 : 1);
+        const int64_t hi = (int64_t)lb[k] + fwd[k] - (fs == KAD_SR_STOP_END ? 1 : 0);
+        if (lo <= hi && hi < block_up && lo > block_down && !any_marked(marked, (uint32_t)lo, (uint32_t)hi)) {
+            out.kind[k] = SR_PLAN_READY;
+            out.ready.push_back(k);
+        } else {
+            out.kind[k] = SR_PLAN_DEFERRED;
+            if (lo <= hi) {
+                if (is_open(fs)) block_up = std::min(block_up, lo);
+                if (is_open(bs)) block_down = std::max(block_down, hi);
+            }
+        }
+        // a later candidate is ready only inside (block_down, block_up), and the blocks only tighten: the part of T
+        // outside them is never asked for again
+        const int64_t mlo = std::max(lo, block_down + 1), mhi = std::min(hi, block_up - 1);
+        if (mlo <= mhi) mark(marked, (uint32_t)mlo, (uint32_t)mhi);
+    }
+    // the ready candidates' T are disjoint: ascending by their first accepting search is ascending by search throughout
+    std::sort(out.ready.begin(), out.ready.end(),
+              [&](uint32_t a, uint32_t b) { return lb[a] - back[a] < lb[b] - back[b] || (lb[a] - back[a] == lb[b] - back[b] && a < b); });
+    for (uint32_t k : out.ready) {
+        const uint32_t fs = stop[k] & 15u, bs = stop[k] >> 4;
+        auto put = [&](uint32_t s, uint8_t want) {
+            out.pair_which.push_back(s);
+            out.pair_cand.push_back(k);
+            out.pair_want.push_back(want);
+        };
+        if (is_far(bs) && (trim[k] & 2u)) put(lb[k] - back[k] - 1, 0);
+        for (uint32_t s = lb[k] - back[k]; s < lb[k] + fwd[k]; s++) put(s, 1);
+        if (is_far(fs) && (trim[k] & 1u)) put(lb[k] + fwd[k], 0);
+    }
+    return KAD_OK;
+}
+
 int sr_mark_plan(uint32_t S, uint32_t q, const uint8_t* node_ids, const uint8_t* clear_bits, const uint8_t* set_bits,
                  uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids, const uint8_t* pair_flags,
                  SrMarkPlan& out, std::string& err) {
@@ -252,5 +340,29 @@ extern "C" int kad_search_trim(uint32_t n, const uint8_t* node_flags, uint32_t s
                                uint32_t* t) {
     if ((n && !node_flags) || !full || !t) return KAD_ERR_INVALID;
     kadplan::search_trim(n, node_flags, search_flags, full, t);
+    return KAD_OK;
+}
+
+extern "C" int kad_sr_plan_round(uint32_t S, uint32_t r, const uint32_t* lb, const uint32_t* fwd, const uint32_t* back,
+                                 const uint8_t* stop, const uint8_t* trim, uint8_t* out_kind, uint32_t* out_pair_which,
+                                 uint32_t* out_pair_cand, uint8_t* out_pair_want, uint32_t* out_n_pairs) {
+    if (!out_n_pairs || (r && (!lb || !fwd || !back || !stop || !trim || !out_kind))) return KAD_ERR_INVALID;
+    if (S && r && (!out_pair_which || !out_pair_cand || !out_pair_want)) return KAD_ERR_INVALID;
+    *out_n_pairs = 0;
+    kadplan::SrRoundPlan plan;
+    std::string err;
+    try {
+        if (int rc = kadplan::sr_round_plan(S, r, lb, fwd, back, stop, trim, plan, err)) return rc;
+    } catch (const std::bad_alloc&) {
+        return KAD_ERR_NOMEM;
+    }
+    const size_t n = plan.pair_which.size();
+    if (r) std::memcpy(out_kind, plan.kind.data(), r);
+    if (n) {
+        std::memcpy(out_pair_which, plan.pair_which.data(), 4 * n);
+        std::memcpy(out_pair_cand, plan.pair_cand.data(), 4 * n);
+        std::memcpy(out_pair_want, plan.pair_want.data(), n);
+    }
+    *out_n_pairs = (uint32_t)n;
     return KAD_OK;
 }

@@ -62,6 +62,33 @@ int searches_apply_plan(uint32_t S, const uint8_t* ids, const uint32_t* erase, u
 int sr_insert_check(uint32_t S, uint32_t m, const uint32_t* which, const uint32_t* off, const uint8_t* cand_flags,
                     std::string& err);
 
+// Host plan of one round of kad_sr_try_insert_tick: opendht_amd.plan_insert_round's rules over the
+// verdicts of the round's remaining candidates, in their order. A candidate probes T = [lb-back-1, lb+fwd] without the
+// ends whose stop is KAD_SR_STOP_END. trim[k]: bit 0 = the forward stopper refused as FAR / FAR_EXPIRED and holds
+// entries past its trim position (full && t < n), bit 1 = the same for the backward stopper.
+//   skipped   fwd + back == 0, both stops END or FAR, neither stopper trims: marks nothing
+//   ready     T meets no T of an earlier candidate that was not skipped, and hi < block_up and lo > block_down
+//   deferred  everything else; with an open stop (KNOWN, FAR_EXPIRED) it blocks from lo upwards (forward stop) or
+//             from hi downwards (backward stop)
+// Every candidate that is not skipped marks T. The pairs of the ready candidates, ascending by search: its accepting
+// searches expect 1, a trimming stopper 0; no two pairs share a search, so there are at most S.
+constexpr uint8_t SR_PLAN_SKIPPED = 0, SR_PLAN_READY = 1, SR_PLAN_DEFERRED = 2;
+
+struct SrRoundPlan {
+    std::vector<uint8_t> kind;         // r
+    std::vector<uint32_t> pair_which;  // the pairs: search, position k of the candidate in the round, expected result
+    std::vector<uint32_t> pair_cand;
+    std::vector<uint8_t> pair_want;
+    std::vector<uint64_t> marked;      // scratch kept between rounds: one bit per search, cleared once per round
+    std::vector<uint32_t> ready;       // scratch: the ready candidates
+};
+
+// Checked first, KAD_ERR_INVALID with `err` set: a stop code above KAD_SR_STOP_FAR_EXPIRED, lb > S, fwd > S - lb,
+// back > lb, or a stop other than END with no search left on its side. Work: O(r + pairs + S/64) plus, for a deferred
+// candidate, its interval's words inside the searches that are not blocked yet.
+int sr_round_plan(uint32_t S, uint32_t r, const uint32_t* lb, const uint32_t* fwd, const uint32_t* back,
+                  const uint8_t* stop, const uint8_t* trim, SrRoundPlan& out, std::string& err);
+
 // The prefix directory of a batch of up to SR_MARK_SMALL_BATCH keys has at most 2^11 + 1 slots (it is staged next to the
 // keys in the scan kernel's LDS), that of a larger batch at most 2^16 + 1.
 constexpr uint32_t SR_MARK_SMALL_BATCH = 4096, SR_MARK_DIR_BITS_SMALL = 11, SR_MARK_DIR_BITS = 16;

@@ -6,6 +6,8 @@ whole tick of candidates and one snapshot of the searches, which searches would 
 walk stopped; try_search_insert turns those verdicts into the exact sequential result while the host touches only
 the searches that accept. try_search_insert_device goes one step further: the accepted inserts
 run on the device as well (kad_sr_insert), in rounds planned by plan_insert_round, and no list is uploaded.
+try_search_insert_tick is the same scheme with the rounds run by the engine in one call per segment of
+the tick (kad_sr_try_insert_tick): the candidates are uploaded once and nothing of the size of the set is read back.
 mark_search_nodes carries the node status changes of a tick (timeouts, replies, candidate bits) to
 every list that holds the node with one kad_sr_mark_nodes, without the host looking for the holders.
 """
@@ -16,8 +18,9 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (KAD_NO_NODE, KAD_SEARCH_NODES, KAD_SN_BAD, KAD_SN_REMOVABLE, KAD_SR_INSERT_OVERFLOW,
-                   KAD_SR_REFILL_OVERFLOW,
-                   KAD_SR_STOP_END, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED, KAD_SR_STOP_KNOWN, check, lib, ptr)
+                   KAD_SR_REFILL_OVERFLOW, KAD_SR_TICK_APPLIED, KAD_SR_TICK_LEFT,
+                   KAD_SR_STOP_END, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED, KAD_SR_STOP_KNOWN, check, lib, ptr,
+                   sr_tick_stats)
 from .table import _as_ids, _stream_of
 
 STOP_NAMES = {KAD_SR_STOP_END: "end", KAD_SR_STOP_KNOWN: "known", KAD_SR_STOP_FAR: "far",
@@ -202,6 +205,31 @@ class DeviceSearches:
         check(lib().kad_sr_insert(self._h, m, ptr(which), ptr(off), ptr(cand), ptr(cand_flags), ptr(ins), ptr(status)),
               "kad_sr_insert")
         return ins, status
+
+    def try_insert_tick(self, cand_ids, cand_flags=None, max_rounds: int = 0) -> dict:
+        """Dht::trySearchInsert of the candidates cand_ids ((q, 20) uint8, in arrival order; cand_flags (q,) uint8
+        KAD_SN_BAD = node->isExpired(), None for all zero) applied to the set in one call (kad_sr_try_insert_tick): the
+        rounds of verdicts, plan and inserts run in the engine, for up to max_rounds rounds (0: no limit). Returns kind
+        (q,) uint8 KAD_SR_TICK_*, round (q,) uint32 and the deciding round's verdict lb, fwd, back (q,) uint32, stop and
+        trim (q,) uint8 for the candidates that are not LEFT, overflow (the searches left untouched because their slab
+        is too small, ascending) and stats (kad_sr_tick_stats as a dict). Synchronous."""
+        cand = _as_ids(cand_ids) if len(cand_ids) else np.zeros((0, 20), np.uint8)
+        q = cand.shape[0]
+        if cand_flags is not None:
+            cand_flags = np.ascontiguousarray(cand_flags, dtype=np.uint8).reshape(-1)
+            if cand_flags.shape[0] != q:
+                raise ValueError("cand_flags must have one byte per candidate")
+        out = {"kind": np.zeros(q, np.uint8), "round": np.zeros(q, np.uint32), "lb": np.zeros(q, np.uint32),
+               "fwd": np.zeros(q, np.uint32), "back": np.zeros(q, np.uint32), "stop": np.zeros(q, np.uint8),
+               "trim": np.zeros(q, np.uint8)}
+        over, n_over, st = np.zeros(max(self.S, 1), np.uint32), C.c_uint32(), sr_tick_stats()
+        check(lib().kad_sr_try_insert_tick(self._h, ptr(cand), ptr(cand_flags), q, max_rounds, ptr(out["kind"]),
+                                           ptr(out["round"]), ptr(out["lb"]), ptr(out["fwd"]), ptr(out["back"]),
+                                           ptr(out["stop"]), ptr(out["trim"]), ptr(over), C.byref(n_over),
+                                           C.byref(st)), "kad_sr_try_insert_tick")
+        out["overflow"] = over[:n_over.value].copy()
+        out["stats"] = {n: getattr(st, n) for n, _ in sr_tick_stats._fields_}
+        return out
 
     def insert_kernel_ms(self) -> float:
         """The device time of the last insert's insert kernel (kad_sr_insert_kernel_ms)."""
@@ -505,6 +533,99 @@ def try_search_insert_device(DS, host, cand_ids, now, max_rounds=8) -> dict:
 
     dirty, pos = [], 0
     left = []  # what the rounds left when the budget ran out, and everything after it: the host path, in order
+    while pos < q:
+        end = pos
+        while end < q and not (host.bad(end) and host.old(end)):
+            end += 1
+        segment = list(range(pos, end))
+        left = left + segment if left else rounds(segment)
+        if end < q:  # the barrier
+            if left:  # the budget is spent: the old candidate waits its turn on the host path
+                left.append(end)
+            else:
+                counts["host"] += 1
+                touched = []
+                lb = DS.try_insert_host(cand[end:end + 1])[0]
+                if _host_walk(host, DS.S, int(lb[0]), end, touched):
+                    touched += [int(s) for s in host.holders(end)]
+                _patch_from_host(DS, host, touched, now)
+        pos = end + 1
+    if left:
+        lbs = DS.try_insert_host(cand[left])[0]
+        for k, j in enumerate(left):
+            counts["host"] += 1
+            was_old = bool(host.bad(j) and host.old(j))
+            holders = [int(s) for s in host.holders(j)] if was_old else []
+            if _host_walk(host, DS.S, int(lbs[k]), j, dirty):
+                dirty += holders
+        _patch_from_host(DS, host, dirty, now)
+    return counts
+
+
+def plan_round(S: int, lb, fwd, back, stop, trim):
+    """plan_insert_round by the engine's planner (kad_sr_plan_round, no device): trim[k] bit 0 = the forward stopper is
+    FAR / FAR_EXPIRED and trims, bit 1 = the backward one. Returns (kind (r,) uint8 KAD_SR_PLAN_*, pair_which, pair_cand
+    (position in the round) uint32 and pair_want uint8, ascending by search)."""
+    lb, fwd, back = (np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (lb, fwd, back))
+    stop, trim = (np.ascontiguousarray(a, dtype=np.uint8).reshape(-1) for a in (stop, trim))
+    r = stop.shape[0]
+    if any(a.shape[0] != r for a in (lb, fwd, back, trim)):
+        raise ValueError("one verdict and one trim byte per candidate")
+    kind = np.zeros(r, np.uint8)
+    pw, pc, want, n = np.zeros(max(S, 1), np.uint32), np.zeros(max(S, 1), np.uint32), np.zeros(max(S, 1), np.uint8), C.c_uint32()
+    rc = lib().kad_sr_plan_round(S, r, ptr(lb), ptr(fwd), ptr(back), ptr(stop), ptr(trim), ptr(kind), ptr(pw), ptr(pc),
+                                 ptr(want), C.byref(n))
+    if rc:
+        raise ValueError(f"kad_sr_plan_round: {rc}: verdicts outside the {S} searches")
+    return kind, pw[:n.value].copy(), pc[:n.value].copy(), want[:n.value].copy()
+
+
+def try_search_insert_tick(DS, host, cand_ids, now, max_rounds=8) -> dict:
+    """try_search_insert_device with the rounds run by the engine: one DS.try_insert_tick per segment
+    of the tick, a segment ending before every old candidate (host.bad(j) and host.old(j), asked when the scan reaches
+    j), which is handled as try_search_insert_device handles it. The host replays the APPLIED candidates in (round,
+    position) order, every answer checked against the verdict; searches the call lists as overflowed are patched from
+    the host's lists, the slabs grown when a list no longer fits, and the call is repeated for what it left while the
+    round budget lasts (max_rounds over the whole tick, None: no limit). What is LEFT then takes the reference walk on
+    the host, in order, followed by one patch. Same `host`, same preconditions and the same counts as
+    try_search_insert_device: {"skipped", "device", "host", "rounds", "pairs", "overflowed"}."""
+    cand = _as_ids(cand_ids)
+    q = cand.shape[0]
+    counts = {"skipped": 0, "device": 0, "host": 0, "rounds": 0, "pairs": 0, "overflowed": 0}
+
+    def replay(rem, r):
+        applied = np.flatnonzero(r["kind"] == KAD_SR_TICK_APPLIED)
+        for k in applied[np.argsort(r["round"][applied], kind="stable")]:
+            j, l, f, b = rem[k], int(r["lb"][k]), int(r["fwd"][k]), int(r["back"][k])
+            for rng, end in ((range(l, DS.S), l + f), (range(l - 1, -1, -1), l - b - 1)):
+                for s in rng:
+                    got = bool(host.insert(s, j))
+                    if got != (s != end):
+                        raise RuntimeError(f"try_search_insert_tick: search {s} answered {got} to candidate {j} "
+                                           "against its verdict")
+                    if not got:
+                        break
+
+    def rounds(rem):
+        """Engine calls over the candidates rem (ascending positions) until none is left or the budget is spent."""
+        # the insert kernel holds a list in one wave: slabs grown past 64 entries leave the rest to the host path
+        while rem and DS.cap <= 64 and (max_rounds is None or counts["rounds"] < max_rounds):
+            flags = np.array([KAD_SN_BAD if host.bad(j) else 0 for j in rem], np.uint8)
+            r = DS.try_insert_tick(cand[rem], flags, 0 if max_rounds is None else max_rounds - counts["rounds"])
+            st = r["stats"]
+            for mine, theirs in (("skipped", "skipped"), ("device", "applied"), ("rounds", "rounds"), ("pairs", "pairs"),
+                                 ("overflowed", "overflowed")):
+                counts[mine] += st[theirs]
+            replay(rem, r)
+            if len(r["overflow"]):
+                _patch_from_host(DS, host, r["overflow"], now)
+            rem = [rem[k] for k in np.flatnonzero(r["kind"] == KAD_SR_TICK_LEFT)]
+            if not len(r["overflow"]):
+                break
+        return rem
+
+    dirty, pos = [], 0
+    left = []  # what the calls left when the budget ran out, and everything after it: the host path, in order
     while pos < q:
         end = pos
         while end < q and not (host.bad(end) and host.old(end)):
