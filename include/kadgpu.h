@@ -739,6 +739,108 @@ int kad_sr_mark_nodes(kad_searches* ss,
  * fix kernel of the last kad_sr_mark_nodes on this set, in milliseconds (0 before the first). */
 int kad_sr_mark_kernel_ms(const kad_searches* ss, float* out_scan_ms, float* out_fix_ms);
 
+/* ---- Dht::searchStep over a set of live searches (dht.cpp:1344-1464) ---- */
+/* Step bits of a member's flag byte, beside KAD_SN_BAD and KAD_SN_REMOVABLE. Like KAD_SN_REMOVABLE the caller maintains
+ * them for the tick's `now`; create, patch, export, kad_searches_apply, kad_sr_refill and kad_sr_insert carry a member's
+ * whole byte, so they travel with their entry. A fresh entry written by insertNode (cand_flags & KAD_SN_BAD) reads
+ * correctly with all of them zero.
+ *   KAD_SN_CANDIDATE  SearchNode::candidate (dht.cpp:270). An entry carrying it also carries KAD_SN_BAD (isBad, :458-460).
+ *   KAD_SN_PENDING    pending(getStatus) (:392-397): some get request to this node is in flight.
+ *   KAD_SN_SYNCED     SearchNode::isSynced(now) (:279-282).
+ *   KAD_SN_NOGET      canGet(now, up, query) (:302-324) is false for a reason other than the node being expired, for the
+ *                     query the search's next searchSendGetValues asks with: the first callback's query, or the default
+ *                     find_node query when there are no callbacks.
+ * An entry is gettable when !(f & NOGET) && (!(f & BAD) || (f & CANDIDATE)). An entry with CANDIDATE whose node is
+ * expired must also carry NOGET (canGet refuses an expired node, and BAD alone no longer says so). SYNCED and the time
+ * clause of canGet both flip at last_get_reply + NODE_EXPIRE_TIME without any event: keeping those deadlines, and
+ * sending the change with kad_sr_mark_entries when one passes, is the host's job, as for KAD_SN_REMOVABLE.
+ * A *pair* of kad_sr_mark_nodes writes the exact byte, of KAD_SN_BAD | KAD_SN_REMOVABLE only, and therefore clears the
+ * entry's step bits; its node ops touch only the two bits they name and keep them. */
+#define KAD_SN_CANDIDATE 0x04u
+#define KAD_SN_PENDING 0x08u
+#define KAD_SN_SYNCED 0x10u
+#define KAD_SN_NOGET 0x20u
+/* Sets and clears step bits of single entries: for every pair k whose search pair_which[k] holds pair_ids[k] among its n
+ * entries, the flag byte becomes (f & ~clear_bits[k]) | set_bits[k]; out_found[k] (may be NULL) = 1 if it was found, else
+ * 0 and nothing changes. Only the four step bits (0x3C) may be named: KAD_SN_BAD and KAD_SN_REMOVABLE move the record and
+ * stay with kad_sr_mark_nodes; no record is rewritten here. Padding slots at or past n never match.
+ * Host arrays, synchronous; as kad_sr_mark_nodes towards queries (it first waits for all device work enqueued before the
+ * call). pair_ids: p x 20 B. clear_bits / set_bits: p bytes each, NULL = all zero. Checked in this order, before any
+ * device work, every failure leaving the set unchanged: NULL ss; NULL pair_which / pair_ids with p > 0; a bit outside
+ * 0x3C in clear_bits or set_bits; clear_bits[k] & set_bits[k] != 0; pair_which[k] >= S; two equal (search, ID) pairs (all
+ * KAD_ERR_INVALID); p == 0 or S == 0 (KAD_OK); cap > 64 (KAD_ERR_UNSUPPORTED). */
+int kad_sr_mark_entries(kad_searches* ss, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids,
+                        const uint8_t* clear_bits, const uint8_t* set_bits, uint8_t* out_found);
+
+/* Mode byte of a stepped search. */
+#define KAD_STEP_APPLY 0x01u           /* kad_sr_step writes the sends and the expiry to the device set */
+#define KAD_STEP_NO_SEND 0x02u         /* no get request is sent (the caller paces this search) */
+#define KAD_STEP_DONE_IF_SYNCED 0x04u  /* no callbacks, announces or listeners: a synced search is set done (:1434) */
+#define KAD_STEP_NO_EXPIRE 0x08u       /* with APPLY: KAD_STEP_EXPIRE is reported, the search is left as it is */
+/* Result bits of a stepped search. */
+#define KAD_STEP_SKIPPED 0x01u    /* KAD_SR_EXPIRED: searchStep returns at :1346; no other bit is set */
+#define KAD_STEP_SHORT 0x02u      /* n - bad < KAD_SEARCH_NODES: the refill test of :1354 without refill_time */
+#define KAD_STEP_SYNCED 0x04u     /* Search::isSynced (:1467-1478) */
+#define KAD_STEP_DONE 0x08u       /* synced under KAD_STEP_DONE_IF_SYNCED: setDone, nothing is sent */
+#define KAD_STEP_EXHAUSTED 0x10u  /* the send loop ended for want of a gettable node, not at 4 requests */
+#define KAD_STEP_EXPIRE 0x20u     /* lead_bad >= min(n, SEARCH_MAX_BAD_NODES = 25) (:1451-1452) */
+typedef struct {
+    uint64_t picks;   /* bit e: entry e of the list gets a request */
+    uint32_t counts;  /* n | bad << 8 | lead_bad << 16 | solicited << 24 */
+    uint32_t bits;    /* KAD_STEP_SKIPPED .. KAD_STEP_EXPIRE */
+} kad_step_out;
+/* searchStep's decision on one list, on the host without a device (as kad_search_trim), from the n <= 64 flag bytes,
+ * search_flags & KAD_SR_EXPIRED and the mode, all from the list as it stands at the call:
+ *   skipped   a search with KAD_SR_EXPIRED: bits = KAD_STEP_SKIPPED, no picks; the counts are still filled.
+ *   counts    bad = entries with BAD; lead_bad = leading BAD entries; solicited = entries with !BAD && PENDING
+ *             (:514-520, :583-597), the latter as it is after the picks.
+ *   short     n - bad < KAD_SEARCH_NODES. refill_time stays with the host; a caller that refills does so with
+ *             kad_sr_refill before the step, as the reference does.
+ *   synced    over the entries that are not BAD, in order: false at the first one without SYNCED among the first 8; true
+ *             only if there is at least one.
+ *   picks     the loop of :1438-1446 over searchSendGetValues (:1171-1196). None if solicited >= 4, if the mode has
+ *             KAD_STEP_NO_SEND, or if the search is synced and the mode has KAD_STEP_DONE_IF_SYNCED (KAD_STEP_DONE).
+ *             Otherwise the gettable entries in list order; a picked entry that is not BAD raises solicited unless it was
+ *             PENDING already (a request for another query is in flight: currentlySolicitedNodeCount counted it before),
+ *             and the loop ends right after the pick that brings it to 4. Picked candidates (BAD) and such PENDING
+ *             entries do not count, so more than four entries can be picked. With room = 4 - solicited and gg = the
+ *             gettable entries that are neither BAD nor PENDING: gg has fewer than room entries: every gettable entry is
+ *             picked and KAD_STEP_EXHAUSTED is set (the host goes on with its further callbacks' queries); otherwise the
+ *             gettable entries up to and including the room-th of gg.
+ *   expire    evaluated after the sends, which do not change BAD; independent of DONE and NO_SEND. An empty live search
+ *             expires, as in the reference.
+ * KAD_STEP_APPLY and KAD_STEP_NO_EXPIRE do not change the answer. NULL node_flags with n > 0, NULL out, n > 64 or a
+ * mode bit outside the four: KAD_ERR_INVALID (kad_last_error is not set: the function lives outside the engine). */
+int kad_search_step(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t mode, kad_step_out* out);
+/* kad_search_step on m lists in CSR form (off[m + 1] into node_flags; search_flags and mode m bytes each, NULL = all
+ * zero), also on the host without a device: what a caller without a device set, or a test, steps its lists with. NULL
+ * off or out, NULL node_flags with off[m] > 0, offsets descending, a list longer than 64 entries or a mode bit outside
+ * the four: KAD_ERR_INVALID, before anything is written. m == 0 reads nothing. */
+int kad_search_step_batch(uint32_t m, const uint32_t* off, const uint8_t* node_flags, const uint8_t* search_flags,
+                          const uint8_t* mode, kad_step_out* out);
+typedef struct {
+    uint32_t synced, expired, skipped, picks;  /* searches with SYNCED, EXPIRE, SKIPPED; entries picked */
+    float kernel_ms;                           /* the call's kernels, between two events of the handle */
+} kad_sr_step_stats;
+/* kad_search_step over the device set: out[k] is the step of search which[k] (which == NULL: every search, out[k] that
+ * of search k, and m must be S) under mode[k] (NULL: all 0). which is strictly ascending and < S. A search whose mode
+ * lacks KAD_STEP_APPLY is only read. With KAD_STEP_APPLY the outcome is written in place:
+ *   sends     every picked entry gets KAD_SN_PENDING | KAD_SN_NOGET: its getStatus[query] is now a pending request, so
+ *             canGet is false for that query.
+ *   expiry    a search with KAD_STEP_EXPIRE (and a mode without KAD_STEP_NO_EXPIRE) becomes what Search::expire()
+ *             (:649-653) leaves: KAD_SR_EXPIRED set and the list empty, its record and slab byte for byte what
+ *             kad_searches_create derives for an empty expired list (keys, tails and flags zero; n, t, full and threshold
+ *             zero). Its picks are still reported, because the reference sends before it expires.
+ * The requests themselves, listen and announce, callbacks and the scheduler stay with the host, which holds the same
+ * lists in the same order. Host arrays, synchronous; as kad_sr_insert towards queries (it first waits for all device
+ * work enqueued before the call). A call in which no search has KAD_STEP_APPLY writes no byte of the set. Checked in this
+ * order, before any device work, every failure leaving the set unchanged: NULL ss or out; which == NULL with m != S;
+ * which not strictly ascending or not < S; a mode bit outside the four (all KAD_ERR_INVALID); m == 0 (KAD_OK);
+ * cap > 64 (KAD_ERR_UNSUPPORTED). Out of host or device memory: KAD_ERR_NOMEM. One lane per search; the scratch is one
+ * allocation per call. out_stats may be NULL. */
+int kad_sr_step(kad_searches* ss, uint32_t m, const uint32_t* which /* NULL: every search */,
+                const uint8_t* mode /* m bytes, NULL: all 0 */, kad_step_out* out, kad_sr_step_stats* out_stats);
+
 /* Per-query family select for NodeCache::getCachedNodes(id, sa_family, count) (node_cache.cpp:36-66:
  * cache_4 or cache_6 by family; Dht::refill asks the search's family, dht.cpp:1650): af[i] = 0 -> table4,
  * 1 -> table6 (KAD_TABLE_SORTED tables; either may be NULL = an empty map). Any count (as kad_nc_closest_batch).

@@ -872,6 +872,16 @@ struct MarkedSearch {
     bool full, expired;
 };
 
+/* One search stepped by SearchesMirror::stepBatch (kad_sr_step): the nodes that get a get request, in list order, the
+ * counts of its list (solicited as it is after the picks) and the KAD_STEP_* result bits. */
+template <class InfoHashT, class NodePtrT>
+struct SteppedSearch {
+    InfoHashT id;
+    std::vector<NodePtrT> picks;
+    uint8_t n, bad, lead_bad, solicited;
+    uint32_t bits;
+};
+
 /* Device mirror of one family's live searches (Dht::searches(af), dht.h) over a map shaped like
  * std::map<InfoHash, std::shared_ptr<Search>>. Reads of a search: id, expired, nodes[i].node->id, nodes[i].isBad().
  * The map must outlive the mirror or the next snapshot. */
@@ -1248,6 +1258,109 @@ public:
         return out;
     }
 
+    /* The step bits of single list entries carried to the device set: one kad_sr_mark_entries. pairs: (search ID, node)
+     * for every entry whose KAD_SN_CANDIDATE, KAD_SN_PENDING, KAD_SN_SYNCED or KAD_SN_NOGET changed (a request sent by
+     * the host itself, a reply, a timeout, a deadline of last_get_reply + NODE_EXPIRE_TIME that passed), and, after a
+     * snapshot, sync or a pair of markNodes (which write the byte without them), for every entry that carries any. The
+     * reference keeps these in the getStatus maps, so the four bits come from the caller: bits(search, search node)
+     * returns them for the entry as the host's list has it now, for the query the search's next searchSendGetValues
+     * asks with (kadgpu.h). The entry gets exactly those four bits; KAD_SN_BAD and KAD_SN_REMOVABLE stay as they are.
+     * Returns, per pair, whether the device's list holds the node; a pair whose node the host's own list does not hold
+     * is not sent and answers 0. Repeated pairs are sent once. A pair always names a mirrored search. */
+    template <class InfoHashT, class NodePtrT, class BitsFn>
+    std::vector<uint8_t> markEntries(const std::vector<std::pair<InfoHashT, NodePtrT>>& pairs, BitsFn bits) {
+        std::vector<uint8_t> out(pairs.size(), 0);
+        if (pairs.empty()) return out;
+        if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::markEntries before snapshot");
+        const uint8_t all = KAD_SN_CANDIDATE | KAD_SN_PENDING | KAD_SN_SYNCED | KAD_SN_NOGET;
+        // (search, node ID, bits, position in pairs), sorted: repeats lie side by side
+        typedef std::pair<std::pair<uint32_t, std::array<uint8_t, KAD_HASH_LEN + 1>>, size_t> Row;
+        std::vector<Row> rows;
+        for (size_t k = 0; k < pairs.size(); k++) {
+            Row r;
+            r.first.first = index_of(id_bytes(pairs[k].first));
+            r.second = k;
+            const auto it = map_->find(pairs[k].first);
+            if (it == map_->end()) throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
+            const uint8_t* nid = id_bytes(pairs[k].second->id);
+            for (const auto& sn : it->second->nodes)
+                if (std::memcmp(id_bytes(sn.node->id), nid, KAD_HASH_LEN) == 0) {
+                    std::memcpy(r.first.second.data(), nid, KAD_HASH_LEN);
+                    r.first.second[KAD_HASH_LEN] = (uint8_t)(bits(*it->second, sn) & all);
+                    rows.push_back(r);
+                    break;
+                }
+        }
+        std::sort(rows.begin(), rows.end());
+        std::vector<uint32_t> pw, first;  // first: per row, the row that was sent for its (search, node)
+        std::vector<uint8_t> pid, clr, set;
+        for (size_t k = 0; k < rows.size(); k++) {
+            const bool repeat = k && rows[k].first.first == rows[k - 1].first.first &&
+                                std::memcmp(rows[k].first.second.data(), rows[k - 1].first.second.data(), KAD_HASH_LEN) == 0;
+            if (!repeat) {
+                pw.push_back(rows[k].first.first);
+                pid.insert(pid.end(), rows[k].first.second.begin(), rows[k].first.second.begin() + KAD_HASH_LEN);
+                set.push_back(rows[k].first.second[KAD_HASH_LEN]);
+                clr.push_back((uint8_t)(all & ~rows[k].first.second[KAD_HASH_LEN]));
+            }
+            first.push_back((uint32_t)pw.size() - 1);
+        }
+        std::vector<uint8_t> found(pw.size());
+        check(kad_sr_mark_entries(ss_, (uint32_t)pw.size(), pw.data(), pid.data(), clr.data(), set.data(), found.data()),
+              "kad_sr_mark_entries");
+        for (size_t k = 0; k < rows.size(); k++) out[rows[k].second] = found[first[k]];
+        return out;
+    }
+
+    /* Dht::searchStep's decision (dht.cpp:1344-1464) on the mirrored searches `ids` (distinct) in one kad_sr_step:
+     * modes[k] = KAD_STEP_* for ids[k] (empty: all 0). Returns, in the order of ids, the nodes that get a get request
+     * (searchSendGetValues' picks, in list order, taken from the host's own list at the picked positions), the counts and
+     * the KAD_STEP_* result bits (kadgpu.h). The device's lists and step bits must be the host's (insertBatch,
+     * refillBatch, markNodes, markEntries, sync). With KAD_STEP_APPLY the device marks the picked entries PENDING | NOGET
+     * and turns a search that expires into an empty expired one; the host then sends the requests, calls expire() on the
+     * searches with KAD_STEP_EXPIRE (unless KAD_STEP_NO_EXPIRE) and reports nothing back for either. Listen and announce
+     * requests, callbacks, refill_time and the scheduler edit stay with the caller; a search that is KAD_STEP_SHORT and
+     * due is refilled with refillBatch before it is stepped. */
+    template <class InfoHashT, class MapT = SearchMapT,
+              class NodePtrT = decltype(std::declval<typename MapT::mapped_type>()->nodes.front().node)>
+    std::vector<SteppedSearch<InfoHashT, NodePtrT>> stepBatch(const std::vector<InfoHashT>& ids,
+                                                              const std::vector<uint8_t>& modes = std::vector<uint8_t>()) {
+        std::vector<SteppedSearch<InfoHashT, NodePtrT>> out(ids.size());
+        if (ids.empty()) return out;
+        if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatch before snapshot");
+        if (!modes.empty() && modes.size() != ids.size())
+            throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatch: one mode per search, or none");
+        std::vector<std::pair<uint32_t, size_t>> order(ids.size());  // (search index, position in ids), ascending
+        for (size_t k = 0; k < ids.size(); k++) order[k] = std::make_pair(index_of(id_bytes(ids[k])), k);
+        std::sort(order.begin(), order.end());
+        std::vector<uint32_t> which(ids.size());
+        std::vector<uint8_t> md(ids.size(), 0);
+        for (size_t k = 0; k < order.size(); k++) {
+            if (k && order[k].first == order[k - 1].first)
+                throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatch: a search listed twice");
+            which[k] = order[k].first;
+            if (!modes.empty()) md[k] = modes[order[k].second];
+        }
+        std::vector<kad_step_out> res(ids.size());
+        check(kad_sr_step(ss_, (uint32_t)which.size(), which.data(), md.data(), res.data(), nullptr), "kad_sr_step");
+        for (size_t k = 0; k < order.size(); k++) {
+            SteppedSearch<InfoHashT, NodePtrT>& o = out[order[k].second];
+            const auto it = map_->find(ids[order[k].second]);
+            if (it == map_->end()) throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
+            o.id = it->first;
+            o.n = (uint8_t)res[k].counts;
+            o.bad = (uint8_t)(res[k].counts >> 8);
+            o.lead_bad = (uint8_t)(res[k].counts >> 16);
+            o.solicited = (uint8_t)(res[k].counts >> 24);
+            o.bits = res[k].bits;
+            if (o.n != it->second->nodes.size())
+                throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatch: the host's list differs from the mirrored one (sync it)");
+            for (uint32_t e = 0; e < o.n; e++)
+                if ((res[k].picks >> e) & 1ull) o.picks.push_back(it->second->nodes[e].node);
+        }
+        return out;
+    }
+
 private:
     template <class InfoHashT, class When>
     void syncAt(const std::vector<InfoHashT>& changed, const When& when) {
@@ -1517,6 +1630,19 @@ public:
     template <class InfoHashT>
     void updateSearches(sa_family_t af, const std::vector<InfoHashT>& erased, const std::vector<InfoHashT>& added) {
         searches(af).update(erased, added, clock_());
+    }
+    /* The step bits of single entries of one family's searches (SearchesMirror::markEntries). */
+    template <class InfoHashT, class NodePtrT, class BitsFn>
+    std::vector<uint8_t> markSearchEntries(sa_family_t af, const std::vector<std::pair<InfoHashT, NodePtrT>>& pairs,
+                                           BitsFn bits) {
+        return searches(af).markEntries(pairs, bits);
+    }
+    /* Dht::searchStep's decision on searches of one family (SearchesMirror::stepBatch). */
+    template <class InfoHashT>
+    auto stepSearches(sa_family_t af, const std::vector<InfoHashT>& ids,
+                      const std::vector<uint8_t>& modes = std::vector<uint8_t>())
+        -> decltype(std::declval<SearchesMirror<SearchMapT>&>().stepBatch(ids, modes)) {
+        return searches(af).stepBatch(ids, modes);
     }
     /* Dht::buckets(af) (dht.h:437-438) */
     const RoutingTableMirror<RoutingTableT>& buckets(sa_family_t af) const { return af == AF_INET ? v4_ : v6_; }

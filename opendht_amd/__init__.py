@@ -19,9 +19,13 @@ from ._lib import KAD_SR_MARK_MAX_NODES
 from ._lib import (KAD_SR_PLAN_DEFERRED, KAD_SR_PLAN_READY, KAD_SR_PLAN_SKIPPED, KAD_SR_TICK_APPLIED, KAD_SR_TICK_LEFT,
                    KAD_SR_TICK_SKIPPED)
 from ._lib import KAD_SWEEP_INCOMING
+from ._lib import (KAD_SN_CANDIDATE, KAD_SN_NOGET, KAD_SN_PENDING, KAD_SN_SYNCED, KAD_STEP_APPLY, KAD_STEP_DONE,
+                   KAD_STEP_DONE_IF_SYNCED, KAD_STEP_EXHAUSTED, KAD_STEP_EXPIRE, KAD_STEP_NO_EXPIRE, KAD_STEP_NO_SEND,
+                   KAD_STEP_SHORT, KAD_STEP_SKIPPED, KAD_STEP_SYNCED)
 from .ingest import ingest
 from .searches import (DeviceSearches, expire_searches, mark_search_nodes, plan_insert_round, plan_round, refill_searches,
-                       start_searches, try_search_insert, try_search_insert_device, try_search_insert_tick)
+                       search_step, search_step_batch, start_searches, step_searches, try_search_insert, try_search_insert_device,
+                       try_search_insert_tick)
 from .table import DeviceTable, nc_closest_dual, rt_closest_dual, rt_responsible_dual
 
 __all__ = [
@@ -38,4 +42,7 @@ __all__ = [
     "KAD_SR_MARK_MAX_NODES", "mark_search_nodes",
     "KAD_SR_PLAN_DEFERRED", "KAD_SR_PLAN_READY", "KAD_SR_PLAN_SKIPPED", "KAD_SR_TICK_APPLIED", "KAD_SR_TICK_LEFT",
     "KAD_SR_TICK_SKIPPED", "plan_round", "try_search_insert_tick",
+    "KAD_SN_CANDIDATE", "KAD_SN_NOGET", "KAD_SN_PENDING", "KAD_SN_SYNCED", "KAD_STEP_APPLY", "KAD_STEP_DONE",
+    "KAD_STEP_DONE_IF_SYNCED", "KAD_STEP_EXHAUSTED", "KAD_STEP_EXPIRE", "KAD_STEP_NO_EXPIRE", "KAD_STEP_NO_SEND",
+    "KAD_STEP_SHORT", "KAD_STEP_SKIPPED", "KAD_STEP_SYNCED", "search_step", "search_step_batch", "step_searches",
 ]

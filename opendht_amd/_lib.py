@@ -46,6 +46,10 @@ KAD_SR_MARK_MAX_NODES = 1 << 20
 KAD_SR_PLAN_SKIPPED, KAD_SR_PLAN_READY, KAD_SR_PLAN_DEFERRED = 0, 1, 2
 KAD_SR_TICK_LEFT, KAD_SR_TICK_SKIPPED, KAD_SR_TICK_APPLIED = 0, 1, 2
 KAD_SR_STOP_END, KAD_SR_STOP_KNOWN, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED = 0, 1, 2, 3
+KAD_SN_CANDIDATE, KAD_SN_PENDING, KAD_SN_SYNCED, KAD_SN_NOGET = 0x04, 0x08, 0x10, 0x20
+KAD_STEP_APPLY, KAD_STEP_NO_SEND, KAD_STEP_DONE_IF_SYNCED, KAD_STEP_NO_EXPIRE = 0x01, 0x02, 0x04, 0x08
+KAD_STEP_SKIPPED, KAD_STEP_SHORT, KAD_STEP_SYNCED, KAD_STEP_DONE, KAD_STEP_EXHAUSTED, KAD_STEP_EXPIRE = (
+    0x01, 0x02, 0x04, 0x08, 0x10, 0x20)
 KAD_SWEEP_INCOMING = 1
 
 
@@ -164,6 +168,10 @@ SIGNATURES = {
     "kad_sr_try_insert_tick": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "kad_sr_mark_nodes": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "kad_sr_mark_kernel_ms": (C.c_int, [_P, _P, _P]),
+    "kad_sr_mark_entries": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "kad_search_step": (C.c_int, [C.c_uint32, _P, C.c_uint32, C.c_uint32, _P]),
+    "kad_search_step_batch": (C.c_int, [C.c_uint32, _P, _P, _P, _P, _P]),
+    "kad_sr_step": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P]),
     "kad_rt_shard_batch": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
                                      _P, _P]),
@@ -272,6 +280,19 @@ class sr_tick_stats(C.Structure):
     """kad_sr_tick_stats"""
     _fields_ = [(n, C.c_uint32) for n in ("rounds", "skipped", "applied", "left", "pairs", "overflowed")] + [
         ("verdict_ms", C.c_float), ("insert_ms", C.c_float)]
+
+
+class step_out(C.Structure):
+    """kad_step_out"""
+    _fields_ = [("picks", C.c_uint64), ("counts", C.c_uint32), ("bits", C.c_uint32)]
+
+
+STEP_OUT_DTYPE = [("picks", "<u8"), ("counts", "<u4"), ("bits", "<u4")]  # kad_step_out as a numpy record
+
+
+class sr_step_stats(C.Structure):
+    """kad_sr_step_stats"""
+    _fields_ = [(n, C.c_uint32) for n in ("synced", "expired", "skipped", "picks")] + [("kernel_ms", C.c_float)]
 
 
 class refresh_diag(C.Structure):

@@ -35,6 +35,12 @@
 // of node IDs, mark_pairs_kernel sets single (search, node) entries, mark_fix_kernel derives the changed searches'
 // records again.
 //
+// kad_sr_step is Dht::searchStep's decision (dht.cpp:1344-1464) on every listed search: step_kernel
+// reads a search's flag bytes and n, one lane per search, and answers which entries get a request and whether the search
+// is synced or expires (kad_step.h, shared with the host's kad_search_step); with KAD_STEP_APPLY the sends are written to
+// the flag bytes and step_expire_kernel empties the searches that expire. kad_sr_mark_entries (entries_kernel) sets and
+// clears the step bits of single entries when replies arrive.
+//
 // kad_searches_apply changes the membership (Dht::search dht.cpp:1673-1735, Dht::expireSearches
 // :1060-1074) and the slab size: the host plans one source word per new search, searches_relayout_kernel gathers the
 // records and slabs into new arrays beside the old ones, searches_rdx_kernel rebuilds the prefix directory, and the
@@ -53,11 +59,13 @@
 #include "../../include/kadgpu.h"
 #include "kad_internal.h"
 #include "kad_searches_plan.h"
+#include "kad_step.h"
 
 // tests/test_refill_abi.py, test_searches_abi.py and test_searches_apply_abi.py hand the argument checks a zeroed
 // buffer for a set: it must read as a set of no searches (S == 0, cap == 0, no pointer followed before the checks end,
 // rf_ms == 0); tests/test_sr_insert_abi.py does the same (in_ms == 0), and tests/test_sr_mark_abi.py (no mark scratch,
-// mk_ms == 0) and tests/test_sr_tick_abi.py (S == 0 answers before anything else of the set is read).
+// mk_ms == 0), tests/test_sr_tick_abi.py (S == 0 answers before anything else of the set is read) and
+// tests/test_sr_step_abi.py (no step events).
 struct kad_searches {
     int device = 0;
     uint32_t S = 0, cap = 0;
@@ -83,6 +91,7 @@ struct kad_searches {
     float mk_ms[2] = {0.f, 0.f};
     // around a kad_sr_try_insert_tick round's verdict kernel, and around its gather and insert kernels
     hipEvent_t tk_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t sp_ev[2] = {nullptr, nullptr};  // around the last kad_sr_step's kernels
 };
 
 namespace {
@@ -976,6 +985,160 @@ __global__ __launch_bounds__(BLOCK) void mark_fix_kernel(DevMark D, uint64_t* __
     }
 }
 
+// ---- kad_sr_mark_entries and kad_sr_step: Dht::searchStep over the set ---------------------------
+// The four step bits of single (search, node) entries: mark_pairs_kernel's walk, then (f & ~clear) | set on the one byte.
+// The pairs of a call are distinct, so every byte has one writer; no record depends on these bits.
+struct DevEntries {
+    const uint32_t* rec;
+    const uint64_t* mkey;
+    const uint32_t* mtail;
+    uint8_t* mflag;
+    uint32_t cap, p;
+    const uint32_t* pw;  // the pairs: search, key, tail, the bits to clear and to set
+    const uint64_t* pkey;
+    const uint32_t* ptail;
+    const uint8_t* pclear;
+    const uint8_t* pset;
+    uint8_t* found;
+};
+
+__global__ __launch_bounds__(BLOCK) void entries_kernel(DevEntries D) {
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= D.p) return;
+    const uint32_t s = D.pw[k], n = min(D.rec[(uint64_t)SREC_WORDS * s + SREC_N], D.cap);
+    const uint64_t x = D.pkey[k];
+    const uint32_t* xt = D.ptail + 3ull * k;
+    const uint32_t x0 = xt[0], x1 = xt[1], x2 = xt[2];
+    const uint64_t* mk = D.mkey + (uint64_t)s * D.cap;
+    const uint32_t* mt = D.mtail + 3ull * s * D.cap;
+    uint32_t at = n;
+    // member()'s walk: keys eight at a time, none predicated, a tail only on a key hit
+    for (uint32_t c = 0; c < n && at == n; c += 8) {
+        uint64_t v[8];
+#pragma unroll
+        for (uint32_t u = 0; u < 8; u++) v[u] = mk[min(c + u, n - 1u)];
+#pragma unroll
+        for (uint32_t u = 0; u < 8; u++) {
+            if (at == n && c + u < n && v[u] == x) {
+                const uint32_t* tl = mt + 3ull * (c + u);
+                if (tl[0] == x0 && tl[1] == x1 && tl[2] == x2) at = c + u;
+            }
+        }
+    }
+    D.found[k] = at < n ? (uint8_t)1 : (uint8_t)0;
+    if (at < n) {
+        uint8_t* f = D.mflag + (uint64_t)s * D.cap + at;
+        const uint8_t have = *f, want = (uint8_t)((have & ~D.pclear[k]) | D.pset[k]);
+        if (want != have) *f = want;
+    }
+}
+
+// One lane per stepped search: n and the expired bit from the record, the flag bytes of the entries below n as words
+// (WIDE, cap a multiple of 16: every slab starts on a 16-byte boundary and is read as 16-byte units; otherwise byte by
+// byte, as a slab then starts anywhere), the words turned into kadstep's five planes, kadstep::decide, one 16-byte store.
+// With KAD_STEP_APPLY the flag units that hold a picked entry are stored back with PENDING | NOGET on it; a search that
+// expires is appended to a list instead, and step_expire_kernel empties it.
+struct DevStep {
+    uint32_t* rec;
+    uint64_t* mkey;
+    uint32_t* mtail;
+    uint8_t* mflag;
+    uint32_t S, cap, m;
+    const uint32_t* which;  // m, NULL: search i
+    const uint8_t* mode;    // m, NULL: all zero
+    u32x4_t* out;           // m
+    uint32_t* n_exp;        // the number of searches to expire, and the searches: room for m
+    uint32_t* exp_list;
+};
+
+template <bool WIDE>
+__global__ __launch_bounds__(BLOCK) void step_kernel(DevStep D) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= D.m) return;
+    const uint32_t s = D.which ? min(D.which[i], D.S - 1u) : i;
+    const uint32_t mode = D.mode ? (uint32_t)D.mode[i] : 0u;
+    const uint32_t* r = D.rec + (uint64_t)SREC_WORDS * s;
+    const uint32_t n = min(r[SREC_N], D.cap);
+    const bool expired = (r[SREC_BITS] & SREC_EXPIRED) != 0;
+    uint8_t* fl = D.mflag + (uint64_t)s * D.cap;
+    uint32_t w[16];  // the flag bytes of entries 4k .. 4k+3; zero from n on (the slab's padding is zero)
+    if (WIDE) {
+        const u32x4_t* fu = reinterpret_cast<const u32x4_t*>(fl);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            u32x4_t u = {0u, 0u, 0u, 0u};
+            if (16u * k < n) u = fu[k];
+            w[4 * k] = u.x;
+            w[4 * k + 1] = u.y;
+            w[4 * k + 2] = u.z;
+            w[4 * k + 3] = u.w;
+        }
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < 16; k++) {
+            uint32_t v = 0;
+#pragma unroll
+            for (uint32_t b = 0; b < 4; b++)
+                if (4u * k + b < n) v |= (uint32_t)fl[4u * k + b] << (8u * b);
+            w[k] = v;
+        }
+    }
+    kadstep::Planes P;
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++) kadstep::add_word(P, w[k], k);
+    const kadstep::Decision d = kadstep::decide(P, n, expired, mode);
+    if (mode & KAD_STEP_APPLY) {
+        if ((d.bits & KAD_STEP_EXPIRE) && !(mode & KAD_STEP_NO_EXPIRE)) {
+            D.exp_list[min(atomicAdd(D.n_exp, 1u), D.m - 1u)] = s;
+        } else if (d.picks) {  // picks lie below n
+            if (WIDE) {
+                u32x4_t* fu = reinterpret_cast<u32x4_t*>(fl);
+#pragma unroll
+                for (uint32_t k = 0; k < 4; k++) {
+                    const u32x4_t a = {kadstep::sent_bytes(d.picks, 4 * k), kadstep::sent_bytes(d.picks, 4 * k + 1),
+                                       kadstep::sent_bytes(d.picks, 4 * k + 2), kadstep::sent_bytes(d.picks, 4 * k + 3)};
+                    if ((d.picks >> (16u * k)) & 0xFFFFull) {
+                        const u32x4_t v = {w[4 * k] | a.x, w[4 * k + 1] | a.y, w[4 * k + 2] | a.z, w[4 * k + 3] | a.w};
+                        fu[k] = v;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < 16; k++) {
+                    const uint32_t v = w[k] | kadstep::sent_bytes(d.picks, k);
+#pragma unroll
+                    for (uint32_t b = 0; b < 4; b++)
+                        if ((d.picks >> (4u * k + b)) & 1ull) fl[4u * k + b] = (uint8_t)(v >> (8u * b));
+                }
+            }
+        }
+    }
+    const u32x4_t o = {(uint32_t)d.picks, (uint32_t)(d.picks >> 32), d.counts, d.bits};
+    __builtin_nontemporal_store(o, D.out + i);
+}
+
+// Search::expire() (dht.cpp:649-653) on the listed searches, one wave per search: the slab all zero and the record's
+// words from n on what kad_searches_create derives for an empty expired list. The search ID stays.
+__global__ __launch_bounds__(BLOCK) void step_expire_kernel(DevStep D) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = rfl(blockIdx.x * REFILL_WAVES + (threadIdx.x >> 6)), waves = gridDim.x * REFILL_WAVES;
+    const uint32_t n_exp = min(rfl(D.n_exp[0]), D.m);
+    for (uint32_t x = wave; x < n_exp; x += waves) {
+        const uint32_t s = min(rfl(D.exp_list[x]), D.S - 1u);
+        if (lane < D.cap) {
+            const uint64_t e0 = (uint64_t)s * D.cap + lane;
+            D.mkey[e0] = 0ull;
+            uint32_t* tl = D.mtail + 3ull * e0;
+            tl[0] = 0u;
+            tl[1] = 0u;
+            tl[2] = 0u;
+            D.mflag[e0] = (uint8_t)0;
+        }
+        if (lane < SREC_WORDS - SREC_N)
+            D.rec[(uint64_t)SREC_WORDS * s + SREC_N + lane] = SREC_N + lane == SREC_BITS ? SREC_EXPIRED : 0u;
+    }
+}
+
 // ---- kad_searches_apply: add and erase searches, grow the slabs -----------------------------------
 // The new set is written beside the old one: every record and slab is gathered from src[s'] (kadplan::SRC_NEW: an
 // inserted search, zero-filled, its record from the 20 uploaded ID bytes). A streaming gather, read once with
@@ -1415,9 +1578,11 @@ int kad_searches_export(const kad_searches* ss, uint8_t* ids, uint8_t* flags, ui
 
 int kad_searches_destroy(kad_searches* ss) {
     if (!ss) return KAD_OK;
-    if (ss->S || ss->rf_ev[0] || ss->in_ev[0] || ss->mk_ev[0] || ss->mk_buf || ss->tk_ev[0]) {  // apply can empty a set that holds events
+    if (ss->S || ss->rf_ev[0] || ss->in_ev[0] || ss->mk_ev[0] || ss->mk_buf || ss->tk_ev[0] || ss->sp_ev[0]) {  // apply can empty a set that holds events
         DeviceGuard g(ss->device);
         (void)hipDeviceSynchronize();
+        for (hipEvent_t e : ss->sp_ev)
+            if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ss->tk_ev)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ss->rf_ev)
@@ -1937,6 +2102,135 @@ int kad_sr_mark_kernel_ms(const kad_searches* ss, float* out_scan_ms, float* out
     *out_scan_ms = ss->mk_ms[0];
     *out_fix_ms = ss->mk_ms[1];
     return KAD_OK;
+}
+
+int kad_sr_mark_entries(kad_searches* ss, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids,
+                        const uint8_t* clear_bits, const uint8_t* set_bits, uint8_t* out_found) {
+    if (!ss) return set_error(KAD_ERR_INVALID, "NULL search set");
+    if (p && (!pair_which || !pair_ids)) return set_error(KAD_ERR_INVALID, "NULL pair arrays");
+    kadplan::SrEntriesPlan plan;
+    std::string err;
+    try {
+        if (int rc = kadplan::sr_entries_plan(ss->S, p, pair_which, pair_ids, clear_bits, set_bits, plan, err))
+            return set_error(rc, err.c_str());
+    } catch (const std::bad_alloc&) {
+        return set_error(KAD_ERR_NOMEM, "mark entries: out of host memory");
+    }
+    if (p == 0 || ss->S == 0) return KAD_OK;
+    if (ss->cap > REFILL_MAX_CAP)
+        return set_error(KAD_ERR_UNSUPPORTED, "kad_sr_mark_entries handles slabs of up to 64 entries");
+    // the call's buffer, one upload: keys, tails, searches, the two op bytes; then the found bytes, one copy back
+    const size_t o_tail = 8ull * p, o_pw = o_tail + 12ull * p, o_clear = o_pw + 4ull * p, o_set = o_clear + p,
+                 o_found = o_set + p, total = o_found + p;
+    uint8_t* h = new (std::nothrow) uint8_t[total];
+    if (!h) return set_error(KAD_ERR_NOMEM, "mark entries: out of host memory");
+    std::memcpy(h, plan.pkey.data(), 8ull * p);
+    std::memcpy(h + o_tail, plan.ptail.data(), 12ull * p);
+    std::memcpy(h + o_pw, plan.pw.data(), 4ull * p);
+    std::memcpy(h + o_clear, plan.pclear.data(), p);
+    std::memcpy(h + o_set, plan.pset.data(), p);
+    DeviceGuard g(ss->device);
+    uint8_t* buf = nullptr;
+    auto done = [&](int r) {
+        if (buf) (void)hipFree(buf);
+        delete[] h;
+        return r;
+    };
+    if (hipDeviceSynchronize() != hipSuccess)  // queries enqueued before the call read the old set
+        return done(set_error(KAD_ERR_HIP, "mark entries: device in error"));
+    if (hipMalloc((void**)&buf, total) != hipSuccess) {
+        (void)hipGetLastError();
+        buf = nullptr;
+        return done(set_error(KAD_ERR_NOMEM, "mark entries: out of device memory"));
+    }
+    if (hipMemcpy(buf, h, o_found, hipMemcpyHostToDevice) != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, "mark entries: H2D failed"));
+    const DevEntries D{ss->rec, ss->mkey, ss->mtail, ss->mflag, ss->cap, p, (const uint32_t*)(buf + o_pw),
+                       (const uint64_t*)buf, (const uint32_t*)(buf + o_tail), buf + o_clear, buf + o_set, buf + o_found};
+    hipLaunchKernelGGL(entries_kernel, dim3((p + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, D);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, (std::string("mark entries: launch failed: ") + hipGetErrorString(le)).c_str()));
+    const hipError_t ce = hipMemcpy(h + o_found, buf + o_found, p, hipMemcpyDeviceToHost);
+    if (ce != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, (std::string("mark entries: D2H failed: ") + hipGetErrorString(ce)).c_str()));
+    if (out_found)
+        for (uint32_t k = 0; k < p; k++) out_found[plan.pord[k]] = h[o_found + k];
+    return done(KAD_OK);
+}
+
+int kad_sr_step(kad_searches* ss, uint32_t m, const uint32_t* which, const uint8_t* mode, kad_step_out* out,
+                kad_sr_step_stats* out_stats) {
+    if (!ss || !out) return set_error(KAD_ERR_INVALID, "NULL search set or output");
+    std::string err;
+    if (int rc = kadplan::sr_step_check(ss->S, m, which, mode, err)) return set_error(rc, err.c_str());
+    kad_sr_step_stats st = {};
+    if (m == 0) {
+        if (out_stats) *out_stats = st;
+        return KAD_OK;
+    }
+    if (ss->cap > REFILL_MAX_CAP) return set_error(KAD_ERR_UNSUPPORTED, "kad_sr_step handles slabs of up to 64 entries");
+    static_assert(sizeof(kad_step_out) == 16, "one 16-byte store per search");
+    bool any_apply = false;
+    for (uint32_t k = 0; mode && k < m && !any_apply; k++) any_apply = (mode[k] & KAD_STEP_APPLY) != 0;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    // the call's scratch, one allocation: the listed searches and the modes (one upload each, when given), the results
+    // (one copy back), the count of searches to expire and their list
+    const size_t o_mode = which ? 4ull * m : 0, o_out = up16(o_mode + (mode ? m : 0)), o_head = o_out + 16ull * m,
+                 o_list = o_head + 16, total = o_list + 4ull * m;
+    DeviceGuard g(ss->device);
+    uint8_t* buf = nullptr;
+    auto done = [&](int r) {
+        if (buf) (void)hipFree(buf);
+        return r;
+    };
+    if (hipDeviceSynchronize() != hipSuccess)  // queries enqueued before the call read the old set
+        return done(set_error(KAD_ERR_HIP, "step: device in error"));
+    if (hipMalloc((void**)&buf, total) != hipSuccess) {
+        (void)hipGetLastError();
+        buf = nullptr;
+        return done(set_error(KAD_ERR_NOMEM, "step: out of device memory"));
+    }
+    for (hipEvent_t& e : ss->sp_ev)
+        if (!e && hipEventCreate(&e) != hipSuccess) return done(set_error(KAD_ERR_HIP, "step: no events"));
+    if ((which && hipMemcpy(buf, which, 4ull * m, hipMemcpyHostToDevice) != hipSuccess) ||
+        (mode && hipMemcpy(buf + o_mode, mode, m, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemsetAsync(buf + o_head, 0, 16, nullptr) != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, "step: H2D failed"));
+    const DevStep D{ss->rec, ss->mkey, ss->mtail, ss->mflag, ss->S, ss->cap, m,
+                    which ? (const uint32_t*)buf : nullptr, mode ? buf + o_mode : nullptr, (u32x4_t*)(buf + o_out),
+                    (uint32_t*)(buf + o_head), (uint32_t*)(buf + o_list)};
+    (void)hipEventRecord(ss->sp_ev[0], nullptr);
+    if (ss->cap % 16 == 0)
+        hipLaunchKernelGGL(step_kernel<true>, dim3((m + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, D);
+    else
+        hipLaunchKernelGGL(step_kernel<false>, dim3((m + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, D);
+    hipError_t le = hipGetLastError();
+    if (le == hipSuccess && any_apply) {  // the grid is sized without the count: the waves stride over what the head says
+        const uint32_t blocks = (m + REFILL_WAVES - 1) / REFILL_WAVES, grid = blocks < MARK_FIX_GRID ? blocks : MARK_FIX_GRID;
+        hipLaunchKernelGGL(step_expire_kernel, dim3(grid), dim3(BLOCK), 0, nullptr, D);
+        le = hipGetLastError();
+    }
+    (void)hipEventRecord(ss->sp_ev[1], nullptr);
+    if (le != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, (std::string("step: launch failed: ") + hipGetErrorString(le)).c_str()));
+    const hipError_t ce = hipMemcpy(out, buf + o_out, 16ull * m, hipMemcpyDeviceToHost);
+    if (ce != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, (std::string("step: D2H failed: ") + hipGetErrorString(ce)).c_str()));
+    if (hipEventElapsedTime(&st.kernel_ms, ss->sp_ev[0], ss->sp_ev[1]) != hipSuccess) {
+        (void)hipGetLastError();
+        st.kernel_ms = 0.f;
+    }
+    if (out_stats) {
+        for (uint32_t k = 0; k < m; k++) {
+            st.synced += (out[k].bits & KAD_STEP_SYNCED) ? 1u : 0u;
+            st.expired += (out[k].bits & KAD_STEP_EXPIRE) ? 1u : 0u;
+            st.skipped += (out[k].bits & KAD_STEP_SKIPPED) ? 1u : 0u;
+            st.picks += (uint32_t)__builtin_popcountll(out[k].picks);
+        }
+        *out_stats = st;
+    }
+    return done(KAD_OK);
 }
 
 int kad_sr_try_insert_batch_host(const kad_searches* ss, const uint8_t* ids, uint32_t q, uint32_t* out_lb,

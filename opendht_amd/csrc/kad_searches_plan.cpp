@@ -8,6 +8,7 @@
 #include <new>
 
 #include "../../include/kadgpu.h"
+#include "kad_step.h"
 
 namespace kadplan {
 namespace {
@@ -334,7 +335,86 @@ int sr_mark_plan(uint32_t S, uint32_t q, const uint8_t* node_ids, const uint8_t*
     return KAD_OK;
 }
 
+int sr_entries_plan(uint32_t S, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids, const uint8_t* clear_bits,
+                    const uint8_t* set_bits, SrEntriesPlan& out, std::string& err) {
+    constexpr uint8_t known = (uint8_t)kadstep::ENTRY_BITS;
+    for (uint32_t k = 0; clear_bits && k < p; k++)
+        if (clear_bits[k] & ~known) return fail(err, KAD_ERR_INVALID, "pair %u: clear_bits outside the step bits", k);
+    for (uint32_t k = 0; set_bits && k < p; k++)
+        if (set_bits[k] & ~known) return fail(err, KAD_ERR_INVALID, "pair %u: set_bits outside the step bits", k);
+    for (uint32_t k = 0; clear_bits && set_bits && k < p; k++)
+        if (clear_bits[k] & set_bits[k]) return fail(err, KAD_ERR_INVALID, "pair %u: a bit both cleared and set", k);
+    for (uint32_t k = 0; k < p; k++)
+        if (pair_which[k] >= S) return fail(err, KAD_ERR_INVALID, "pair %u: search %u not below S", k, pair_which[k]);
+    out.pord.resize(p);
+    for (uint32_t k = 0; k < p; k++) out.pord[k] = k;
+    std::sort(out.pord.begin(), out.pord.end(), [&](uint32_t a, uint32_t b) {
+        if (pair_which[a] != pair_which[b]) return pair_which[a] < pair_which[b];
+        return std::memcmp(pair_ids + 20ull * a, pair_ids + 20ull * b, KAD_HASH_LEN) < 0;
+    });
+    for (uint32_t k = 1; k < p; k++) {
+        const uint32_t a = out.pord[k - 1], b = out.pord[k];
+        if (pair_which[a] == pair_which[b] && std::memcmp(pair_ids + 20ull * a, pair_ids + 20ull * b, KAD_HASH_LEN) == 0)
+            return fail(err, KAD_ERR_INVALID, "pairs %u and %u are equal", a, b);
+    }
+    out.pw.resize(p);
+    out.pkey.resize(p);
+    out.ptail.resize(3ull * p);
+    out.pclear.resize(p);
+    out.pset.resize(p);
+    for (uint32_t k = 0; k < p; k++) {
+        const uint32_t a = out.pord[k];
+        const uint8_t* id = pair_ids + 20ull * a;
+        out.pw[k] = pair_which[a];
+        out.pkey[k] = top64(id);
+        for (int w = 0; w < 3; w++) out.ptail[3ull * k + w] = be32(id + 8 + 4 * w);
+        out.pclear[k] = clear_bits ? clear_bits[a] : (uint8_t)0;
+        out.pset[k] = set_bits ? set_bits[a] : (uint8_t)0;
+    }
+    return KAD_OK;
+}
+
+int sr_step_check(uint32_t S, uint32_t m, const uint32_t* which, const uint8_t* mode, std::string& err) {
+    if (!which && m != S) return fail(err, KAD_ERR_INVALID, "which == NULL steps every search: m must be S");
+    for (uint32_t k = 0; which && k < m; k++)
+        if (which[k] >= S || (k && which[k] <= which[k - 1]))
+            return fail(err, KAD_ERR_INVALID, "stepped searches must be strictly ascending and below S");
+    for (uint32_t k = 0; mode && k < m; k++)
+        if (mode[k] & ~kadstep::MODE_BITS) return fail(err, KAD_ERR_INVALID, "search %u: unknown mode bit", k);
+    return KAD_OK;
+}
+
 }  // namespace kadplan
+
+extern "C" int kad_search_step(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t mode,
+                               kad_step_out* out) {
+    if ((n && !node_flags) || !out || n > 64u || (mode & ~kadstep::MODE_BITS)) return KAD_ERR_INVALID;
+    kadstep::Planes P;
+    for (uint32_t i = 0; 4u * i < n; i++) {  // the flag bytes four at a time, as the kernel's words hold them
+        uint32_t w = 0;
+        for (uint32_t b = 0; b < 4u && 4u * i + b < n; b++) w |= (uint32_t)node_flags[4u * i + b] << (8u * b);
+        kadstep::add_word(P, w, i);
+    }
+    const kadstep::Decision d = kadstep::decide(P, n, (search_flags & KAD_SR_EXPIRED) != 0, mode);
+    out->picks = d.picks;
+    out->counts = d.counts;
+    out->bits = d.bits;
+    return KAD_OK;
+}
+
+extern "C" int kad_search_step_batch(uint32_t m, const uint32_t* off, const uint8_t* node_flags,
+                                     const uint8_t* search_flags, const uint8_t* mode, kad_step_out* out) {
+    if (m == 0) return KAD_OK;
+    if (!off || !out || (off[m] && !node_flags)) return KAD_ERR_INVALID;
+    for (uint32_t k = 0; k < m; k++)
+        if (off[k + 1] < off[k] || off[k + 1] - off[k] > 64u || (mode && (mode[k] & ~kadstep::MODE_BITS)))
+            return KAD_ERR_INVALID;
+    for (uint32_t k = 0; k < m; k++)
+        if (int rc = kad_search_step(off[k + 1] - off[k], node_flags + off[k], search_flags ? search_flags[k] : 0u,
+                                     mode ? mode[k] : 0u, out + k))
+            return rc;
+    return KAD_OK;
+}
 
 extern "C" int kad_search_trim(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t* full,
                                uint32_t* t) {

@@ -120,4 +120,25 @@ int sr_mark_plan(uint32_t S, uint32_t q, const uint8_t* node_ids, const uint8_t*
                  uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids, const uint8_t* pair_flags,
                  SrMarkPlan& out, std::string& err);
 
+// Host plan of kad_sr_mark_entries: the pairs in the device's word form with their ops, sorted by
+// (search, ID) so that equal pairs are found, and the permutation that brings out_found back into the caller's order.
+struct SrEntriesPlan {
+    std::vector<uint32_t> pord;   // p: sorted position -> the caller's pair index
+    std::vector<uint32_t> pw;     // p search indices, ascending
+    std::vector<uint64_t> pkey;   // p keys, p x 3 tails
+    std::vector<uint32_t> ptail;
+    std::vector<uint8_t> pclear, pset;  // p bytes each
+};
+
+// Checked in this order, all KAD_ERR_INVALID with `err` set: a bit outside the four step bits in clear_bits or set_bits
+// (NULL: all zero); clear_bits[k] & set_bits[k] != 0; pair_which[k] >= S; two equal (search, ID) pairs. p == 0 reads
+// nothing. O(p log p).
+int sr_entries_plan(uint32_t S, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids, const uint8_t* clear_bits,
+                    const uint8_t* set_bits, SrEntriesPlan& out, std::string& err);
+
+// The list checks of kad_sr_step, in this order: which == NULL with m != S; which[0..m) not strictly ascending or not
+// below S; a byte of mode[0..m) (NULL: all zero) with a bit outside the four mode bits. KAD_OK or KAD_ERR_INVALID with
+// `err` set.
+int sr_step_check(uint32_t S, uint32_t m, const uint32_t* which, const uint8_t* mode, std::string& err);
+
 }  // namespace kadplan

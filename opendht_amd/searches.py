@@ -10,6 +10,8 @@ try_search_insert_tick is the same scheme with the rounds run
 the tick (kad_sr_try_insert_tick): the candidates are uploaded once and nothing of the size of the set is read back.
 mark_search_nodes carries the node status changes of a tick (timeouts, replies, candidate bits) to
 every list that holds the node with one kad_sr_mark_nodes, without the host looking for the holders.
+step_searches (DESIGN.md §7.19) is Dht::searchStep's decision on every stepped search with one kad_sr_step: which
+entries get a get request, which searches are synced and which expire, applied to the device set in place.
 """
 from __future__ import annotations
 
@@ -19,8 +21,9 @@ import numpy as np
 
 from ._lib import (KAD_NO_NODE, KAD_SEARCH_NODES, KAD_SN_BAD, KAD_SN_REMOVABLE, KAD_SR_INSERT_OVERFLOW,
                    KAD_SR_REFILL_OVERFLOW, KAD_SR_TICK_APPLIED, KAD_SR_TICK_LEFT,
-                   KAD_SR_STOP_END, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED, KAD_SR_STOP_KNOWN, check, lib, ptr,
-                   sr_tick_stats)
+                   KAD_SR_STOP_END, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED, KAD_SR_STOP_KNOWN, KAD_STEP_APPLY,
+                   KAD_STEP_DONE, KAD_STEP_EXHAUSTED, KAD_STEP_EXPIRE, KAD_STEP_NO_EXPIRE, KAD_STEP_SHORT,
+                   KAD_STEP_SKIPPED, KAD_STEP_SYNCED, STEP_OUT_DTYPE, check, lib, ptr, sr_step_stats, sr_tick_stats)
 from .table import _as_ids, _stream_of
 
 STOP_NAMES = {KAD_SR_STOP_END: "end", KAD_SR_STOP_KNOWN: "known", KAD_SR_STOP_FAR: "far",
@@ -273,6 +276,43 @@ class DeviceSearches:
         a, b = C.c_float(), C.c_float()
         check(lib().kad_sr_mark_kernel_ms(self._h, C.byref(a), C.byref(b)), "kad_sr_mark_kernel_ms")
         return a.value, b.value
+
+    def mark_entries(self, which, ids, clear_bits=None, set_bits=None):
+        """Step bits of single entries (kad_sr_mark_entries): for every pair (which[k], ids[k]) whose search holds the ID,
+        the flag byte becomes (f & ~clear_bits[k]) | set_bits[k] ((p,) uint8 over KAD_SN_CANDIDATE | KAD_SN_PENDING |
+        KAD_SN_SYNCED | KAD_SN_NOGET, None for all zero). Returns found (p,) uint8. Synchronous."""
+        pw = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
+        p = pw.shape[0]
+        pid = _as_ids(ids) if p else np.zeros((0, 20), np.uint8)
+        if clear_bits is not None:
+            clear_bits = np.ascontiguousarray(clear_bits, dtype=np.uint8).reshape(-1)
+        if set_bits is not None:
+            set_bits = np.ascontiguousarray(set_bits, dtype=np.uint8).reshape(-1)
+        if pid.shape[0] != p or any(b is not None and b.shape[0] != p for b in (clear_bits, set_bits)):
+            raise ValueError("ids, clear_bits and set_bits must have one entry per pair")
+        found = np.zeros(p, np.uint8)
+        check(lib().kad_sr_mark_entries(self._h, p, ptr(pw), ptr(pid), ptr(clear_bits), ptr(set_bits), ptr(found)),
+              "kad_sr_mark_entries")
+        return found
+
+    def step(self, which=None, modes=None) -> dict:
+        """Dht::searchStep's decision on the searches `which` (strictly ascending indices; None: every search) under
+        modes ((m,) uint8 of KAD_STEP_APPLY | KAD_STEP_NO_SEND | KAD_STEP_DONE_IF_SYNCED | KAD_STEP_NO_EXPIRE, or one
+        int for all, None for 0), on the device (kad_sr_step). Returns picks (m,) uint64 (bit e: entry e gets a
+        request), n, bad, lead_bad, solicited (m,) uint8, bits (m,) uint32 of KAD_STEP_SKIPPED .. KAD_STEP_EXPIRE, and
+        stats (kad_sr_step_stats as a dict). With KAD_STEP_APPLY the sends and expiries are written to the set.
+        Synchronous."""
+        if which is not None:
+            which = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
+        m = self.S if which is None else which.shape[0]
+        if modes is not None:
+            modes = (np.full(m, modes, np.uint8) if np.isscalar(modes)
+                     else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1))
+            if modes.shape[0] != m:
+                raise ValueError("modes must have one byte per stepped search")
+        out, st = np.zeros(m, STEP_OUT_DTYPE), sr_step_stats()
+        check(lib().kad_sr_step(self._h, m, ptr(which), ptr(modes), ptr(out), C.byref(st)), "kad_sr_step")
+        return _step_fields(out, {n: getattr(st, n) for n, _ in sr_step_stats._fields_})
 
     @property
     def refill_kernel_ms(self) -> float:
@@ -695,6 +735,89 @@ def mark_search_nodes(DS, host, nodes, pairs, now) -> dict:
             out["short"].append(int(s))
         else:
             out["neither"].append(int(s))
+    return out
+
+
+def _step_fields(out, stats=None) -> dict:
+    """kad_step_out records as separate arrays."""
+    c = out["counts"]
+    r = {"picks": out["picks"].copy(), "n": (c & 0xFF).astype(np.uint8), "bad": ((c >> 8) & 0xFF).astype(np.uint8),
+         "lead_bad": ((c >> 16) & 0xFF).astype(np.uint8), "solicited": (c >> 24).astype(np.uint8),
+         "bits": out["bits"].copy()}
+    if stats is not None:
+        r["stats"] = stats
+    return r
+
+
+def search_step(node_flags, search_flags: int = 0, mode: int = 0) -> dict:
+    """Dht::searchStep's decision on one list from its flag bytes, on the host without a device (kad_search_step):
+    picks (int mask of list positions), n, bad, lead_bad, solicited and bits (ints)."""
+    fl = np.ascontiguousarray(node_flags, dtype=np.uint8).reshape(-1)
+    out = np.zeros(1, STEP_OUT_DTYPE)
+    rc = lib().kad_search_step(fl.shape[0], ptr(fl) if fl.shape[0] else None, search_flags, mode, ptr(out))
+    if rc != 0:
+        raise ValueError(f"kad_search_step: {rc}: more than 64 entries or an unknown mode bit")
+    return {k: int(v[0]) for k, v in _step_fields(out).items()}
+
+
+def search_step_batch(off, node_flags, search_flags=None, modes=None) -> dict:
+    """search_step on m lists in CSR form (off (m + 1,) uint32 into node_flags; search_flags and modes (m,) uint8 or
+    None), on the host (kad_search_step_batch): the arrays DeviceSearches.step returns, without stats."""
+    off = np.ascontiguousarray(off, dtype=np.uint32).reshape(-1)
+    m = off.shape[0] - 1
+    fl = np.ascontiguousarray(node_flags, dtype=np.uint8).reshape(-1)
+    sf = None if search_flags is None else np.ascontiguousarray(search_flags, dtype=np.uint8).reshape(-1)
+    md = None if modes is None else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1)
+    if m < 0 or fl.shape[0] < int(off[-1]) or any(a is not None and a.shape[0] != m for a in (sf, md)):
+        raise ValueError("off needs m + 1 offsets into node_flags, search_flags and modes one byte per list")
+    out = np.zeros(m, STEP_OUT_DTYPE)
+    rc = lib().kad_search_step_batch(m, ptr(off), ptr(fl) if fl.shape[0] else None, ptr(sf), ptr(md), ptr(out))
+    if rc != 0:
+        raise ValueError(f"kad_search_step_batch: {rc}: offsets descending, a list of more than 64 entries or an unknown mode bit")
+    return _step_fields(out)
+
+
+def step_searches(DS, host, which, modes, now) -> dict:
+    """Dht::searchStep's sends and expiries for the searches `which` (strictly ascending indices; None: all) of DS under
+    modes (as DeviceSearches.step) with one device step, replayed on the host's searches. `host` holds
+    the real searches in the same list order: step(s, mode, now) -> (picks, n, bad, lead_bad, solicited, bits), its own
+    entry-by-entry searchStep on search s as it stands, changing nothing (picks the list positions it would send to, in
+    order); send(s, pos, now) marks the get request to entry pos of search s as sent (getStatus[query] pending);
+    expire(s) is Search::expire(). Every search's device answer is checked against host.step before anything is
+    replayed; a difference raises. A search whose mode has KAD_STEP_APPLY then gets its sends and, unless the mode has
+    KAD_STEP_NO_EXPIRE, its expiry on the host, as the device has applied them to its own copy; nothing is uploaded.
+
+    Returns {"synced", "short", "done", "exhausted", "expire", "skipped"} (lists of searches), "picks" ({search: list
+    positions}) and "stats"."""
+    idx = np.arange(DS.S, dtype=np.uint32) if which is None else np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
+    m = idx.shape[0]
+    md = np.zeros(m, np.uint8) if modes is None else (np.full(m, modes, np.uint8) if np.isscalar(modes)
+                                                      else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1))
+    want = [host.step(int(s), int(md[k]), now) for k, s in enumerate(idx)]
+    r = DS.step(which, md)
+    out = {"synced": [], "short": [], "done": [], "exhausted": [], "expire": [], "skipped": [], "picks": {},
+           "stats": r["stats"]}
+    names = ((KAD_STEP_SYNCED, "synced"), (KAD_STEP_SHORT, "short"), (KAD_STEP_DONE, "done"),
+             (KAD_STEP_EXHAUSTED, "exhausted"), (KAD_STEP_EXPIRE, "expire"), (KAD_STEP_SKIPPED, "skipped"))
+    for k, s in enumerate(idx):
+        picks = [e for e in range(64) if (int(r["picks"][k]) >> e) & 1]
+        got = (picks, int(r["n"][k]), int(r["bad"][k]), int(r["lead_bad"][k]), int(r["solicited"][k]), int(r["bits"][k]))
+        w = want[k]
+        if got != (list(w[0]),) + tuple(int(v) for v in w[1:]):
+            raise RuntimeError(f"step_searches: search {int(s)} stepped to {w} on the host, {got} on the device")
+    for k, s in enumerate(idx):
+        s, bits = int(s), int(r["bits"][k])
+        picks = want[k][0]
+        if picks:
+            out["picks"][s] = list(picks)
+        for bit, name in names:
+            if bits & bit:
+                out[name].append(s)
+        if md[k] & KAD_STEP_APPLY:
+            for e in picks:
+                host.send(s, e, now)
+            if bits & KAD_STEP_EXPIRE and not md[k] & KAD_STEP_NO_EXPIRE:
+                host.expire(s)
     return out
 
 
