@@ -841,6 +841,78 @@ typedef struct {
 int kad_sr_step(kad_searches* ss, uint32_t m, const uint32_t* which /* NULL: every search */,
                 const uint8_t* mode /* m bytes, NULL: all 0 */, kad_step_out* out, kad_sr_step_stats* out_stats);
 
+/* ---- The whole searchStep: the listen and announce sends beside the get requests ---- */
+/* The two remaining bits of a member's flag byte. The caller maintains them for the tick's `now`, as it does
+ * KAD_SN_SYNCED, KAD_SN_NOGET and KAD_SN_REMOVABLE; they ride where the four step bits ride and travel with their entry.
+ *   KAD_SN_LISTEN_DUE    some listener l of the search has n.getListenTime(l.query) <= now (dht.cpp:447-453)
+ *   KAD_SN_ANNOUNCE_DUE  some announce a of the search has n.getAnnounceTime(a.value->id) <= now (:431-441)
+ * Both flip on events (a reply, a new listener or announce) and at deadlines the host keeps: reply_time +
+ * LISTEN_EXPIRE_TIME - REANNOUNCE_MARGIN and acked.second - REANNOUNCE_MARGIN. They do not depend on KAD_SN_SYNCED: the
+ * loops test isSynced themselves. All-zero on a fresh entry is conservative: nothing is sent until the caller marks it.
+ * A pair of kad_sr_mark_nodes clears them with the step bits. Bits are read literally: an entry with KAD_SN_SYNCED and
+ * KAD_SN_BAD but without KAD_SN_CANDIDATE is the caller's inconsistency, and nothing is repaired. */
+#define KAD_SN_LISTEN_DUE 0x40u
+#define KAD_SN_ANNOUNCE_DUE 0x80u
+/* kad_sr_mark_entries for the two due bits: the same contract and the same checks in the same order, with the mask 0xC0
+ * in place of 0x3C (a step bit named here is KAD_ERR_INVALID, as a due bit is there). */
+int kad_sr_mark_due(kad_searches* ss, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids,
+                    const uint8_t* clear_bits, const uint8_t* set_bits, uint8_t* out_found);
+
+/* Further mode bits, for kad_search_step_full[_batch] and kad_sr_step_full only (the calls above refuse them). */
+#define KAD_STEP_LISTEN 0x10u        /* the search's listeners are not empty: the listen loop of :1384-1428 runs */
+#define KAD_STEP_ANNOUNCE 0x20u      /* its announces are not empty: searchSendAnnounceValue (:1237-1339) runs */
+#define KAD_STEP_PROBE_BLOCKS 0x40u  /* the probe query Select{Id, SeqNum} satisfies the search's get query, so a probed
+                                      * node cannot get (pending_sq_status): announce picks also count as NOGET */
+typedef struct {
+    uint64_t picks;     /* bit e: entry e gets a get request, as kad_step_out */
+    uint64_t listen;    /* bit e: entry e gets the listen requests that are due on it */
+    uint64_t announce;  /* bit e: entry e gets the announce probe */
+    uint32_t counts;    /* n | bad << 8 | lead_bad << 16 | solicited << 24, solicited after all three loops */
+    uint32_t bits;      /* KAD_STEP_SKIPPED .. KAD_STEP_EXPIRE */
+} kad_step_full_out;
+/* kad_search_step with the two send loops that precede the get loop, from the list as it stands at the call:
+ *   skipped   as kad_search_step; the three masks are zero.
+ *   listen    only if the search is synced and the mode has KAD_STEP_LISTEN. The entries in order; one without SYNCED is
+ *             passed over and not counted; a synced one is picked if it has LISTEN_DUE; every synced entry without
+ *             CANDIDATE counts towards LISTEN_NODES = 4, picked or not, and the walk ends after the fourth.
+ *   announce  only if the search is synced and the mode has KAD_STEP_ANNOUNCE. An entry is picked if it has SYNCED and
+ *             ANNOUNCE_DUE; only picked entries without CANDIDATE count towards TARGET_NODES = 8, and the walk ends after
+ *             the eighth.
+ *   picks     kad_search_step's, on the list with every announce pick made PENDING (the probe is a get request and is
+ *             counted by currentlySolicitedNodeCount) and, under KAD_STEP_PROBE_BLOCKS, NOGET. KAD_STEP_NO_SEND concerns
+ *             this loop only. solicited is the value after all three loops.
+ * A mode without KAD_STEP_LISTEN and KAD_STEP_ANNOUNCE gives kad_search_step's picks, counts and bits and zero listen and
+ * announce masks. KAD_ERR_INVALID as kad_search_step, and for: a mode bit outside the seven (0x80); KAD_STEP_DONE_IF_SYNCED
+ * with KAD_STEP_LISTEN or KAD_STEP_ANNOUNCE (it means "no listeners, no announces"); KAD_STEP_PROBE_BLOCKS without
+ * KAD_STEP_ANNOUNCE. */
+int kad_search_step_full(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t mode,
+                         kad_step_full_out* out);
+/* kad_search_step_full on m lists in CSR form, as kad_search_step_batch. */
+int kad_search_step_full_batch(uint32_t m, const uint32_t* off, const uint8_t* node_flags, const uint8_t* search_flags,
+                               const uint8_t* mode, kad_step_full_out* out);
+typedef struct {
+    uint32_t synced, expired, skipped;    /* searches with SYNCED, EXPIRE, SKIPPED */
+    uint32_t picks, listens, announces;   /* entries picked by the get loop, the listen loop, the announce loop */
+    float kernel_ms;                      /* the call's kernels, between two events of the handle */
+} kad_sr_step_full_stats;
+/* kad_search_step_full over the device set, with kad_sr_step's contract: which (NULL: every search, m must be S),
+ * strictly ascending and < S; mode NULL: all 0; a search whose mode lacks KAD_STEP_APPLY is only read, and a call in which
+ * none has it writes no byte of the set. With KAD_STEP_APPLY each picked entry's byte f becomes
+ *   (f | PENDING where picks | announce | NOGET where picks, and where announce under PROBE_BLOCKS)
+ *     & ~LISTEN_DUE where listen & ~ANNOUNCE_DUE where announce:
+ * after sendListen every listener's getListenTime on that node is max, and with the probe pending getAnnounceTime is max
+ * for every value. A search with KAD_STEP_EXPIRE (mode without KAD_STEP_NO_EXPIRE) becomes an empty expired search as
+ * with kad_sr_step; its three masks are still reported, because the reference sends before it expires.
+ * isDone(get) and checkAnnounced of :1359-1376, getNextStepTime, the requests themselves, callbacks and the scheduler
+ * stay with the host. Host arrays, synchronous, as kad_sr_step towards queries. Checked in this order, before any device
+ * work, every failure leaving the set unchanged: NULL ss or out; which == NULL with m != S; which not strictly ascending
+ * or not < S; an invalid mode (bit 0x80, DONE_IF_SYNCED with LISTEN or ANNOUNCE, PROBE_BLOCKS without ANNOUNCE) (all
+ * KAD_ERR_INVALID); m == 0 (KAD_OK); cap > 64 (KAD_ERR_UNSUPPORTED). Out of host or device memory: KAD_ERR_NOMEM. One
+ * lane per search; the scratch is one allocation per call. out_stats may be NULL. */
+int kad_sr_step_full(kad_searches* ss, uint32_t m, const uint32_t* which /* NULL: every search */,
+                     const uint8_t* mode /* m bytes, NULL: all 0 */, kad_step_full_out* out,
+                     kad_sr_step_full_stats* out_stats);
+
 /* Per-query family select for NodeCache::getCachedNodes(id, sa_family, count) (node_cache.cpp:36-66:
  * cache_4 or cache_6 by family; Dht::refill asks the search's family, dht.cpp:1650): af[i] = 0 -> table4,
  * 1 -> table6 (KAD_TABLE_SORTED tables; either may be NULL = an empty map). Any count (as kad_nc_closest_batch).

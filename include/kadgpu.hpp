@@ -882,6 +882,16 @@ struct SteppedSearch {
     uint32_t bits;
 };
 
+/* One search stepped by SearchesMirror::stepBatchFull (kad_sr_step_full): SteppedSearch with the nodes that get the
+ * listen requests due on them and the nodes that get the announce probe, each in list order. */
+template <class InfoHashT, class NodePtrT>
+struct FullySteppedSearch {
+    InfoHashT id;
+    std::vector<NodePtrT> picks, listen, announce;
+    uint8_t n, bad, lead_bad, solicited;
+    uint32_t bits;
+};
+
 /* Device mirror of one family's live searches (Dht::searches(af), dht.h) over a map shaped like
  * std::map<InfoHash, std::shared_ptr<Search>>. Reads of a search: id, expired, nodes[i].node->id, nodes[i].isBad().
  * The map must outlive the mirror or the next snapshot. */
@@ -1269,10 +1279,19 @@ public:
      * is not sent and answers 0. Repeated pairs are sent once. A pair always names a mirrored search. */
     template <class InfoHashT, class NodePtrT, class BitsFn>
     std::vector<uint8_t> markEntries(const std::vector<std::pair<InfoHashT, NodePtrT>>& pairs, BitsFn bits) {
+        return markBits(pairs, bits, (uint8_t)(KAD_SN_CANDIDATE | KAD_SN_PENDING | KAD_SN_SYNCED | KAD_SN_NOGET),
+                        &kad_sr_mark_entries, "kad_sr_mark_entries");
+    }
+
+    /* markEntries and markDue: the bits `all` of every pair's entry become bits(search, search node) & all, with `call`. */
+    template <class InfoHashT, class NodePtrT, class BitsFn>
+    std::vector<uint8_t> markBits(const std::vector<std::pair<InfoHashT, NodePtrT>>& pairs, BitsFn bits, const uint8_t all,
+                                  int (*call)(kad_searches*, uint32_t, const uint32_t*, const uint8_t*, const uint8_t*,
+                                              const uint8_t*, uint8_t*),
+                                  const char* what) {
         std::vector<uint8_t> out(pairs.size(), 0);
         if (pairs.empty()) return out;
         if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::markEntries before snapshot");
-        const uint8_t all = KAD_SN_CANDIDATE | KAD_SN_PENDING | KAD_SN_SYNCED | KAD_SN_NOGET;
         // (search, node ID, bits, position in pairs), sorted: repeats lie side by side
         typedef std::pair<std::pair<uint32_t, std::array<uint8_t, KAD_HASH_LEN + 1>>, size_t> Row;
         std::vector<Row> rows;
@@ -1306,8 +1325,7 @@ public:
             first.push_back((uint32_t)pw.size() - 1);
         }
         std::vector<uint8_t> found(pw.size());
-        check(kad_sr_mark_entries(ss_, (uint32_t)pw.size(), pw.data(), pid.data(), clr.data(), set.data(), found.data()),
-              "kad_sr_mark_entries");
+        check(call(ss_, (uint32_t)pw.size(), pw.data(), pid.data(), clr.data(), set.data(), found.data()), what);
         for (size_t k = 0; k < rows.size(); k++) out[rows[k].second] = found[first[k]];
         return out;
     }
@@ -1357,6 +1375,67 @@ public:
                 throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatch: the host's list differs from the mirrored one (sync it)");
             for (uint32_t e = 0; e < o.n; e++)
                 if ((res[k].picks >> e) & 1ull) o.picks.push_back(it->second->nodes[e].node);
+        }
+        return out;
+    }
+
+    /* The two due bits of single list entries carried to the device set: one kad_sr_mark_due. pairs as for markEntries:
+     * every entry whose KAD_SN_LISTEN_DUE or KAD_SN_ANNOUNCE_DUE changed (a listen or put reply, a new listener or
+     * announce, a deadline of reply_time + LISTEN_EXPIRE_TIME - REANNOUNCE_MARGIN or acked.second - REANNOUNCE_MARGIN that
+     * passed) and, after a snapshot, sync or a pair of markNodes, every entry that carries any. The reference keeps these
+     * in listenStatus, acked and probe_query, so the bits come from the caller: bits(search, search node) returns them
+     * for the entry as the host has it now. The entry gets exactly those two bits; the other six stay as they are.
+     * Returns as markEntries does. */
+    template <class InfoHashT, class NodePtrT, class BitsFn>
+    std::vector<uint8_t> markDue(const std::vector<std::pair<InfoHashT, NodePtrT>>& pairs, BitsFn bits) {
+        return markBits(pairs, bits, (uint8_t)(KAD_SN_LISTEN_DUE | KAD_SN_ANNOUNCE_DUE), &kad_sr_mark_due, "kad_sr_mark_due");
+    }
+
+    /* stepBatch with the listen requests and the announce probes of a synced search (kad_sr_step_full): modes[k] may
+     * also carry KAD_STEP_LISTEN (the search has listeners), KAD_STEP_ANNOUNCE (it has announces) and
+     * KAD_STEP_PROBE_BLOCKS (kadgpu.h). Returns per search the three node lists in list order, plus the counts and bits.
+     * With KAD_STEP_APPLY the device also clears the due bit of every entry a loop sent to and marks the probed entries
+     * PENDING; the host sends the listens, the probes and the gets in that order. isDone(get) and checkAnnounced
+     * (dht.cpp:1359-1376), getNextStepTime and the requests themselves stay with the caller. */
+    template <class InfoHashT, class MapT = SearchMapT,
+              class NodePtrT = decltype(std::declval<typename MapT::mapped_type>()->nodes.front().node)>
+    std::vector<FullySteppedSearch<InfoHashT, NodePtrT>> stepBatchFull(
+        const std::vector<InfoHashT>& ids, const std::vector<uint8_t>& modes = std::vector<uint8_t>()) {
+        std::vector<FullySteppedSearch<InfoHashT, NodePtrT>> out(ids.size());
+        if (ids.empty()) return out;
+        if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatchFull before snapshot");
+        if (!modes.empty() && modes.size() != ids.size())
+            throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatchFull: one mode per search, or none");
+        std::vector<std::pair<uint32_t, size_t>> order(ids.size());  // (search index, position in ids), ascending
+        for (size_t k = 0; k < ids.size(); k++) order[k] = std::make_pair(index_of(id_bytes(ids[k])), k);
+        std::sort(order.begin(), order.end());
+        std::vector<uint32_t> which(ids.size());
+        std::vector<uint8_t> md(ids.size(), 0);
+        for (size_t k = 0; k < order.size(); k++) {
+            if (k && order[k].first == order[k - 1].first)
+                throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatchFull: a search listed twice");
+            which[k] = order[k].first;
+            if (!modes.empty()) md[k] = modes[order[k].second];
+        }
+        std::vector<kad_step_full_out> res(ids.size());
+        check(kad_sr_step_full(ss_, (uint32_t)which.size(), which.data(), md.data(), res.data(), nullptr), "kad_sr_step_full");
+        for (size_t k = 0; k < order.size(); k++) {
+            FullySteppedSearch<InfoHashT, NodePtrT>& o = out[order[k].second];
+            const auto it = map_->find(ids[order[k].second]);
+            if (it == map_->end()) throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
+            o.id = it->first;
+            o.n = (uint8_t)res[k].counts;
+            o.bad = (uint8_t)(res[k].counts >> 8);
+            o.lead_bad = (uint8_t)(res[k].counts >> 16);
+            o.solicited = (uint8_t)(res[k].counts >> 24);
+            o.bits = res[k].bits;
+            if (o.n != it->second->nodes.size())
+                throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatchFull: the host's list differs from the mirrored one (sync it)");
+            for (uint32_t e = 0; e < o.n; e++) {
+                if ((res[k].picks >> e) & 1ull) o.picks.push_back(it->second->nodes[e].node);
+                if ((res[k].listen >> e) & 1ull) o.listen.push_back(it->second->nodes[e].node);
+                if ((res[k].announce >> e) & 1ull) o.announce.push_back(it->second->nodes[e].node);
+            }
         }
         return out;
     }
@@ -1643,6 +1722,18 @@ public:
                       const std::vector<uint8_t>& modes = std::vector<uint8_t>())
         -> decltype(std::declval<SearchesMirror<SearchMapT>&>().stepBatch(ids, modes)) {
         return searches(af).stepBatch(ids, modes);
+    }
+    /* The due bits of single entries of one family's searches (SearchesMirror::markDue). */
+    template <class InfoHashT, class NodePtrT, class BitsFn>
+    std::vector<uint8_t> markSearchDue(sa_family_t af, const std::vector<std::pair<InfoHashT, NodePtrT>>& pairs, BitsFn bits) {
+        return searches(af).markDue(pairs, bits);
+    }
+    /* The whole searchStep's decision on searches of one family (SearchesMirror::stepBatchFull). */
+    template <class InfoHashT>
+    auto stepSearchesFull(sa_family_t af, const std::vector<InfoHashT>& ids,
+                          const std::vector<uint8_t>& modes = std::vector<uint8_t>())
+        -> decltype(std::declval<SearchesMirror<SearchMapT>&>().stepBatchFull(ids, modes)) {
+        return searches(af).stepBatchFull(ids, modes);
     }
     /* Dht::buckets(af) (dht.h:437-438) */
     const RoutingTableMirror<RoutingTableT>& buckets(sa_family_t af) const { return af == AF_INET ? v4_ : v6_; }

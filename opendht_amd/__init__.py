@@ -22,9 +22,11 @@ from ._lib import KAD_SWEEP_INCOMING
 from ._lib import (KAD_SN_CANDIDATE, KAD_SN_NOGET, KAD_SN_PENDING, KAD_SN_SYNCED, KAD_STEP_APPLY, KAD_STEP_DONE,
                    KAD_STEP_DONE_IF_SYNCED, KAD_STEP_EXHAUSTED, KAD_STEP_EXPIRE, KAD_STEP_NO_EXPIRE, KAD_STEP_NO_SEND,
                    KAD_STEP_SHORT, KAD_STEP_SKIPPED, KAD_STEP_SYNCED)
+from ._lib import KAD_SN_ANNOUNCE_DUE, KAD_SN_LISTEN_DUE, KAD_STEP_ANNOUNCE, KAD_STEP_LISTEN, KAD_STEP_PROBE_BLOCKS
 from .ingest import ingest
 from .searches import (DeviceSearches, expire_searches, mark_search_nodes, plan_insert_round, plan_round, refill_searches,
-                       search_step, search_step_batch, start_searches, step_searches, try_search_insert, try_search_insert_device,
+                       search_step, search_step_batch, search_step_full, search_step_full_batch, start_searches,
+                       step_searches, step_searches_full, try_search_insert, try_search_insert_device,
                        try_search_insert_tick)
 from .table import DeviceTable, nc_closest_dual, rt_closest_dual, rt_responsible_dual
 
@@ -45,4 +47,6 @@ __all__ = [
     "KAD_SN_CANDIDATE", "KAD_SN_NOGET", "KAD_SN_PENDING", "KAD_SN_SYNCED", "KAD_STEP_APPLY", "KAD_STEP_DONE",
     "KAD_STEP_DONE_IF_SYNCED", "KAD_STEP_EXHAUSTED", "KAD_STEP_EXPIRE", "KAD_STEP_NO_EXPIRE", "KAD_STEP_NO_SEND",
     "KAD_STEP_SHORT", "KAD_STEP_SKIPPED", "KAD_STEP_SYNCED", "search_step", "search_step_batch", "step_searches",
+    "KAD_SN_ANNOUNCE_DUE", "KAD_SN_LISTEN_DUE", "KAD_STEP_ANNOUNCE", "KAD_STEP_LISTEN", "KAD_STEP_PROBE_BLOCKS",
+    "search_step_full", "search_step_full_batch", "step_searches_full",
 ]

@@ -50,6 +50,8 @@ KAD_SN_CANDIDATE, KAD_SN_PENDING, KAD_SN_SYNCED, KAD_SN_NOGET = 0x04, 0x08, 0x10
 KAD_STEP_APPLY, KAD_STEP_NO_SEND, KAD_STEP_DONE_IF_SYNCED, KAD_STEP_NO_EXPIRE = 0x01, 0x02, 0x04, 0x08
 KAD_STEP_SKIPPED, KAD_STEP_SHORT, KAD_STEP_SYNCED, KAD_STEP_DONE, KAD_STEP_EXHAUSTED, KAD_STEP_EXPIRE = (
     0x01, 0x02, 0x04, 0x08, 0x10, 0x20)
+KAD_SN_LISTEN_DUE, KAD_SN_ANNOUNCE_DUE = 0x40, 0x80
+KAD_STEP_LISTEN, KAD_STEP_ANNOUNCE, KAD_STEP_PROBE_BLOCKS = 0x10, 0x20, 0x40
 KAD_SWEEP_INCOMING = 1
 
 
@@ -172,6 +174,10 @@ SIGNATURES = {
     "kad_search_step": (C.c_int, [C.c_uint32, _P, C.c_uint32, C.c_uint32, _P]),
     "kad_search_step_batch": (C.c_int, [C.c_uint32, _P, _P, _P, _P, _P]),
     "kad_sr_step": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P]),
+    "kad_sr_mark_due": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "kad_search_step_full": (C.c_int, [C.c_uint32, _P, C.c_uint32, C.c_uint32, _P]),
+    "kad_search_step_full_batch": (C.c_int, [C.c_uint32, _P, _P, _P, _P, _P]),
+    "kad_sr_step_full": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P]),
     "kad_rt_shard_batch": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
                                      _P, _P]),
@@ -293,6 +299,22 @@ STEP_OUT_DTYPE = [("picks", "<u8"), ("counts", "<u4"), ("bits", "<u4")]  # kad_s
 class sr_step_stats(C.Structure):
     """kad_sr_step_stats"""
     _fields_ = [(n, C.c_uint32) for n in ("synced", "expired", "skipped", "picks")] + [("kernel_ms", C.c_float)]
+
+
+class step_full_out(C.Structure):
+    """kad_step_full_out"""
+    _fields_ = [("picks", C.c_uint64), ("listen", C.c_uint64), ("announce", C.c_uint64), ("counts", C.c_uint32),
+                ("bits", C.c_uint32)]
+
+
+# kad_step_full_out as a numpy record
+STEP_FULL_OUT_DTYPE = [("picks", "<u8"), ("listen", "<u8"), ("announce", "<u8"), ("counts", "<u4"), ("bits", "<u4")]
+
+
+class sr_step_full_stats(C.Structure):
+    """kad_sr_step_full_stats"""
+    _fields_ = [(n, C.c_uint32) for n in ("synced", "expired", "skipped", "picks", "listens", "announces")] + [
+        ("kernel_ms", C.c_float)]
 
 
 class refresh_diag(C.Structure):

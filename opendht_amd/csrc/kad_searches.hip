@@ -41,6 +41,10 @@
 // the flag bytes and step_expire_kernel empties the searches that expire. kad_sr_mark_entries (entries_kernel) sets and
 // clears the step bits of single entries when replies arrive.
 //
+// kad_sr_step_full is the same step with the two send loops that precede the get loop: the listen
+// requests and the announce probes of a synced search, from two more bits of the flag byte (kad_sr_mark_due sets them).
+// step_full_kernel is step_kernel's shape over seven planes and kadstep::decide_full; step_expire_kernel is shared.
+//
 // kad_searches_apply changes the membership (Dht::search dht.cpp:1673-1735, Dht::expireSearches
 // :1060-1074) and the slab size: the host plans one source word per new search, searches_relayout_kernel gathers the
 // records and slabs into new arrays beside the old ones, searches_rdx_kernel rebuilds the prefix directory, and the
@@ -65,7 +69,7 @@
 // buffer for a set: it must read as a set of no searches (S == 0, cap == 0, no pointer followed before the checks end,
 // rf_ms == 0); tests/test_sr_insert_abi.py does the same (in_ms == 0), and tests/test_sr_mark_abi.py (no mark scratch,
 // mk_ms == 0), tests/test_sr_tick_abi.py (S == 0 answers before anything else of the set is read) and
-// tests/test_sr_step_abi.py (no step events).
+// tests/test_sr_step_abi.py and tests/test_sr_stepfull_abi.py (no step events).
 struct kad_searches {
     int device = 0;
     uint32_t S = 0, cap = 0;
@@ -91,7 +95,7 @@ struct kad_searches {
     float mk_ms[2] = {0.f, 0.f};
     // around a kad_sr_try_insert_tick round's verdict kernel, and around its gather and insert kernels
     hipEvent_t tk_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t sp_ev[2] = {nullptr, nullptr};  // around the last kad_sr_step's kernels
+    hipEvent_t sp_ev[2] = {nullptr, nullptr};  // around the last kad_sr_step's or kad_sr_step_full's kernels
 };
 
 namespace {
@@ -1139,6 +1143,84 @@ __global__ __launch_bounds__(BLOCK) void step_expire_kernel(DevStep D) {
     }
 }
 
+// kad_sr_step_full: step_kernel's lane, loads and stores over all eight bits of the flag bytes. The
+// words become kadstep's seven planes, kadstep::decide_full answers the three send loops, and the 32-byte result goes out
+// as two 16-byte stores (D.out holds 2 m units). With KAD_STEP_APPLY an entry picked by any loop is rewritten: PENDING for
+// a get request or a probe, NOGET for a get request (and for a probe under PROBE_BLOCKS), LISTEN_DUE and ANNOUNCE_DUE
+// cleared where that loop sent; only the units that hold such an entry are stored back.
+template <bool WIDE>
+__global__ __launch_bounds__(BLOCK) void step_full_kernel(DevStep D) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= D.m) return;
+    const uint32_t s = D.which ? min(D.which[i], D.S - 1u) : i;
+    const uint32_t mode = D.mode ? (uint32_t)D.mode[i] : 0u;
+    const uint32_t* r = D.rec + (uint64_t)SREC_WORDS * s;
+    const uint32_t n = min(r[SREC_N], D.cap);
+    const bool expired = (r[SREC_BITS] & SREC_EXPIRED) != 0;
+    uint8_t* fl = D.mflag + (uint64_t)s * D.cap;
+    uint32_t w[16];  // the flag bytes of entries 4k .. 4k+3; zero from n on (the slab's padding is zero)
+    if (WIDE) {
+        const u32x4_t* fu = reinterpret_cast<const u32x4_t*>(fl);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            u32x4_t u = {0u, 0u, 0u, 0u};
+            if (16u * k < n) u = fu[k];
+            w[4 * k] = u.x;
+            w[4 * k + 1] = u.y;
+            w[4 * k + 2] = u.z;
+            w[4 * k + 3] = u.w;
+        }
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < 16; k++) {
+            uint32_t v = 0;
+#pragma unroll
+            for (uint32_t b = 0; b < 4; b++)
+                if (4u * k + b < n) v |= (uint32_t)fl[4u * k + b] << (8u * b);
+            w[k] = v;
+        }
+    }
+    kadstep::PlanesFull P;
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++) kadstep::add_word_full(P, w[k], k);
+    const kadstep::DecisionFull d = kadstep::decide_full(P, n, expired, mode);
+    if (mode & KAD_STEP_APPLY) {
+        const uint64_t pend = d.picks | d.announce, noget = d.picks | ((mode & KAD_STEP_PROBE_BLOCKS) ? d.announce : 0ull);
+        const uint64_t touched = pend | d.listen;  // all below n
+        if ((d.bits & KAD_STEP_EXPIRE) && !(mode & KAD_STEP_NO_EXPIRE)) {
+            D.exp_list[min(atomicAdd(D.n_exp, 1u), D.m - 1u)] = s;
+        } else if (touched) {
+            uint32_t v[16];
+#pragma unroll
+            for (uint32_t k = 0; k < 16; k++)
+                v[k] = (w[k] | kadstep::mask_bytes(pend, k, KAD_SN_PENDING) | kadstep::mask_bytes(noget, k, KAD_SN_NOGET)) &
+                       ~kadstep::mask_bytes(d.listen, k, KAD_SN_LISTEN_DUE) &
+                       ~kadstep::mask_bytes(d.announce, k, KAD_SN_ANNOUNCE_DUE);
+            if (WIDE) {
+                u32x4_t* fu = reinterpret_cast<u32x4_t*>(fl);
+#pragma unroll
+                for (uint32_t k = 0; k < 4; k++) {
+                    if ((touched >> (16u * k)) & 0xFFFFull) {
+                        const u32x4_t u = {v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]};
+                        fu[k] = u;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < 16; k++) {
+#pragma unroll
+                    for (uint32_t b = 0; b < 4; b++)
+                        if ((touched >> (4u * k + b)) & 1ull) fl[4u * k + b] = (uint8_t)(v[k] >> (8u * b));
+                }
+            }
+        }
+    }
+    const u32x4_t o0 = {(uint32_t)d.picks, (uint32_t)(d.picks >> 32), (uint32_t)d.listen, (uint32_t)(d.listen >> 32)};
+    const u32x4_t o1 = {(uint32_t)d.announce, (uint32_t)(d.announce >> 32), d.counts, d.bits};
+    __builtin_nontemporal_store(o0, D.out + 2ull * i);
+    __builtin_nontemporal_store(o1, D.out + 2ull * i + 1ull);
+}
+
 // ---- kad_searches_apply: add and erase searches, grow the slabs -----------------------------------
 // The new set is written beside the old one: every record and slab is gathered from src[s'] (kadplan::SRC_NEW: an
 // inserted search, zero-filled, its record from the 20 uploaded ID bytes). A streaming gather, read once with
@@ -2104,21 +2186,27 @@ int kad_sr_mark_kernel_ms(const kad_searches* ss, float* out_scan_ms, float* out
     return KAD_OK;
 }
 
-int kad_sr_mark_entries(kad_searches* ss, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids,
-                        const uint8_t* clear_bits, const uint8_t* set_bits, uint8_t* out_found) {
+namespace {
+// kad_sr_mark_entries and kad_sr_mark_due: one body, the bits that may be named decided by `plan_fn`
+using EntriesPlanFn = int (*)(uint32_t, uint32_t, const uint32_t*, const uint8_t*, const uint8_t*, const uint8_t*,
+                              kadplan::SrEntriesPlan&, std::string&);
+
+int mark_entry_bits(kad_searches* ss, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids,
+                    const uint8_t* clear_bits, const uint8_t* set_bits, uint8_t* out_found, EntriesPlanFn plan_fn,
+                    const char* unsupported) {
     if (!ss) return set_error(KAD_ERR_INVALID, "NULL search set");
     if (p && (!pair_which || !pair_ids)) return set_error(KAD_ERR_INVALID, "NULL pair arrays");
     kadplan::SrEntriesPlan plan;
     std::string err;
     try {
-        if (int rc = kadplan::sr_entries_plan(ss->S, p, pair_which, pair_ids, clear_bits, set_bits, plan, err))
+        if (int rc = plan_fn(ss->S, p, pair_which, pair_ids, clear_bits, set_bits, plan, err))
             return set_error(rc, err.c_str());
     } catch (const std::bad_alloc&) {
         return set_error(KAD_ERR_NOMEM, "mark entries: out of host memory");
     }
     if (p == 0 || ss->S == 0) return KAD_OK;
     if (ss->cap > REFILL_MAX_CAP)
-        return set_error(KAD_ERR_UNSUPPORTED, "kad_sr_mark_entries handles slabs of up to 64 entries");
+        return set_error(KAD_ERR_UNSUPPORTED, unsupported);
     // the call's buffer, one upload: keys, tails, searches, the two op bytes; then the found bytes, one copy back
     const size_t o_tail = 8ull * p, o_pw = o_tail + 12ull * p, o_clear = o_pw + 4ull * p, o_set = o_clear + p,
                  o_found = o_set + p, total = o_found + p;
@@ -2157,6 +2245,19 @@ int kad_sr_mark_entries(kad_searches* ss, uint32_t p, const uint32_t* pair_which
     if (out_found)
         for (uint32_t k = 0; k < p; k++) out_found[plan.pord[k]] = h[o_found + k];
     return done(KAD_OK);
+}
+}  // namespace
+
+int kad_sr_mark_entries(kad_searches* ss, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids,
+                        const uint8_t* clear_bits, const uint8_t* set_bits, uint8_t* out_found) {
+    return mark_entry_bits(ss, p, pair_which, pair_ids, clear_bits, set_bits, out_found, kadplan::sr_entries_plan,
+                           "kad_sr_mark_entries handles slabs of up to 64 entries");
+}
+
+int kad_sr_mark_due(kad_searches* ss, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids,
+                    const uint8_t* clear_bits, const uint8_t* set_bits, uint8_t* out_found) {
+    return mark_entry_bits(ss, p, pair_which, pair_ids, clear_bits, set_bits, out_found, kadplan::sr_due_plan,
+                           "kad_sr_mark_due handles slabs of up to 64 entries");
 }
 
 int kad_sr_step(kad_searches* ss, uint32_t m, const uint32_t* which, const uint8_t* mode, kad_step_out* out,
@@ -2227,6 +2328,82 @@ int kad_sr_step(kad_searches* ss, uint32_t m, const uint32_t* which, const uint8
             st.expired += (out[k].bits & KAD_STEP_EXPIRE) ? 1u : 0u;
             st.skipped += (out[k].bits & KAD_STEP_SKIPPED) ? 1u : 0u;
             st.picks += (uint32_t)__builtin_popcountll(out[k].picks);
+        }
+        *out_stats = st;
+    }
+    return done(KAD_OK);
+}
+
+int kad_sr_step_full(kad_searches* ss, uint32_t m, const uint32_t* which, const uint8_t* mode, kad_step_full_out* out,
+                     kad_sr_step_full_stats* out_stats) {
+    if (!ss || !out) return set_error(KAD_ERR_INVALID, "NULL search set or output");
+    std::string err;
+    if (int rc = kadplan::sr_step_full_check(ss->S, m, which, mode, err)) return set_error(rc, err.c_str());
+    kad_sr_step_full_stats st = {};
+    if (m == 0) {
+        if (out_stats) *out_stats = st;
+        return KAD_OK;
+    }
+    if (ss->cap > REFILL_MAX_CAP)
+        return set_error(KAD_ERR_UNSUPPORTED, "kad_sr_step_full handles slabs of up to 64 entries");
+    static_assert(sizeof(kad_step_full_out) == 32, "two 16-byte stores per search");
+    bool any_apply = false;
+    for (uint32_t k = 0; mode && k < m && !any_apply; k++) any_apply = (mode[k] & KAD_STEP_APPLY) != 0;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    // the call's scratch, one allocation, laid out as kad_sr_step's with 32 bytes of result per search
+    const size_t o_mode = which ? 4ull * m : 0, o_out = up16(o_mode + (mode ? m : 0)), o_head = o_out + 32ull * m,
+                 o_list = o_head + 16, total = o_list + 4ull * m;
+    DeviceGuard g(ss->device);
+    uint8_t* buf = nullptr;
+    auto done = [&](int r) {
+        if (buf) (void)hipFree(buf);
+        return r;
+    };
+    if (hipDeviceSynchronize() != hipSuccess)  // queries enqueued before the call read the old set
+        return done(set_error(KAD_ERR_HIP, "step full: device in error"));
+    if (hipMalloc((void**)&buf, total) != hipSuccess) {
+        (void)hipGetLastError();
+        buf = nullptr;
+        return done(set_error(KAD_ERR_NOMEM, "step full: out of device memory"));
+    }
+    for (hipEvent_t& e : ss->sp_ev)
+        if (!e && hipEventCreate(&e) != hipSuccess) return done(set_error(KAD_ERR_HIP, "step full: no events"));
+    if ((which && hipMemcpy(buf, which, 4ull * m, hipMemcpyHostToDevice) != hipSuccess) ||
+        (mode && hipMemcpy(buf + o_mode, mode, m, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemsetAsync(buf + o_head, 0, 16, nullptr) != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, "step full: H2D failed"));
+    const DevStep D{ss->rec, ss->mkey, ss->mtail, ss->mflag, ss->S, ss->cap, m,
+                    which ? (const uint32_t*)buf : nullptr, mode ? buf + o_mode : nullptr, (u32x4_t*)(buf + o_out),
+                    (uint32_t*)(buf + o_head), (uint32_t*)(buf + o_list)};
+    (void)hipEventRecord(ss->sp_ev[0], nullptr);
+    if (ss->cap % 16 == 0)
+        hipLaunchKernelGGL(step_full_kernel<true>, dim3((m + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, D);
+    else
+        hipLaunchKernelGGL(step_full_kernel<false>, dim3((m + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, D);
+    hipError_t le = hipGetLastError();
+    if (le == hipSuccess && any_apply) {  // the grid is sized without the count: the waves stride over what the head says
+        const uint32_t blocks = (m + REFILL_WAVES - 1) / REFILL_WAVES, grid = blocks < MARK_FIX_GRID ? blocks : MARK_FIX_GRID;
+        hipLaunchKernelGGL(step_expire_kernel, dim3(grid), dim3(BLOCK), 0, nullptr, D);
+        le = hipGetLastError();
+    }
+    (void)hipEventRecord(ss->sp_ev[1], nullptr);
+    if (le != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, (std::string("step full: launch failed: ") + hipGetErrorString(le)).c_str()));
+    const hipError_t ce = hipMemcpy(out, buf + o_out, 32ull * m, hipMemcpyDeviceToHost);
+    if (ce != hipSuccess)
+        return done(set_error(KAD_ERR_HIP, (std::string("step full: D2H failed: ") + hipGetErrorString(ce)).c_str()));
+    if (hipEventElapsedTime(&st.kernel_ms, ss->sp_ev[0], ss->sp_ev[1]) != hipSuccess) {
+        (void)hipGetLastError();
+        st.kernel_ms = 0.f;
+    }
+    if (out_stats) {
+        for (uint32_t k = 0; k < m; k++) {
+            st.synced += (out[k].bits & KAD_STEP_SYNCED) ? 1u : 0u;
+            st.expired += (out[k].bits & KAD_STEP_EXPIRE) ? 1u : 0u;
+            st.skipped += (out[k].bits & KAD_STEP_SKIPPED) ? 1u : 0u;
+            st.picks += (uint32_t)__builtin_popcountll(out[k].picks);
+            st.listens += (uint32_t)__builtin_popcountll(out[k].listen);
+            st.announces += (uint32_t)__builtin_popcountll(out[k].announce);
         }
         *out_stats = st;
     }

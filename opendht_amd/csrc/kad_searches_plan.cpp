@@ -335,13 +335,15 @@ int sr_mark_plan(uint32_t S, uint32_t q, const uint8_t* node_ids, const uint8_t*
     return KAD_OK;
 }
 
-int sr_entries_plan(uint32_t S, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids, const uint8_t* clear_bits,
-                    const uint8_t* set_bits, SrEntriesPlan& out, std::string& err) {
-    constexpr uint8_t known = (uint8_t)kadstep::ENTRY_BITS;
+namespace {
+// sr_entries_plan and sr_due_plan: the same plan over the bits `known`, named `what` in the errors
+int entries_plan_over(uint8_t known, const char* what, uint32_t S, uint32_t p, const uint32_t* pair_which,
+                      const uint8_t* pair_ids, const uint8_t* clear_bits, const uint8_t* set_bits, SrEntriesPlan& out,
+                      std::string& err) {
     for (uint32_t k = 0; clear_bits && k < p; k++)
-        if (clear_bits[k] & ~known) return fail(err, KAD_ERR_INVALID, "pair %u: clear_bits outside the step bits", k);
+        if (clear_bits[k] & ~known) return fail(err, KAD_ERR_INVALID, "pair %u: clear_bits outside the %s bits", k, what);
     for (uint32_t k = 0; set_bits && k < p; k++)
-        if (set_bits[k] & ~known) return fail(err, KAD_ERR_INVALID, "pair %u: set_bits outside the step bits", k);
+        if (set_bits[k] & ~known) return fail(err, KAD_ERR_INVALID, "pair %u: set_bits outside the %s bits", k, what);
     for (uint32_t k = 0; clear_bits && set_bits && k < p; k++)
         if (clear_bits[k] & set_bits[k]) return fail(err, KAD_ERR_INVALID, "pair %u: a bit both cleared and set", k);
     for (uint32_t k = 0; k < p; k++)
@@ -373,6 +375,17 @@ int sr_entries_plan(uint32_t S, uint32_t p, const uint32_t* pair_which, const ui
     }
     return KAD_OK;
 }
+}  // namespace
+
+int sr_entries_plan(uint32_t S, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids, const uint8_t* clear_bits,
+                    const uint8_t* set_bits, SrEntriesPlan& out, std::string& err) {
+    return entries_plan_over((uint8_t)kadstep::ENTRY_BITS, "step", S, p, pair_which, pair_ids, clear_bits, set_bits, out, err);
+}
+
+int sr_due_plan(uint32_t S, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids, const uint8_t* clear_bits,
+                const uint8_t* set_bits, SrEntriesPlan& out, std::string& err) {
+    return entries_plan_over((uint8_t)kadstep::DUE_BITS, "due", S, p, pair_which, pair_ids, clear_bits, set_bits, out, err);
+}
 
 int sr_step_check(uint32_t S, uint32_t m, const uint32_t* which, const uint8_t* mode, std::string& err) {
     if (!which && m != S) return fail(err, KAD_ERR_INVALID, "which == NULL steps every search: m must be S");
@@ -384,7 +397,46 @@ int sr_step_check(uint32_t S, uint32_t m, const uint32_t* which, const uint8_t* 
     return KAD_OK;
 }
 
+int sr_step_full_check(uint32_t S, uint32_t m, const uint32_t* which, const uint8_t* mode, std::string& err) {
+    if (int rc = sr_step_check(S, m, which, nullptr, err)) return rc;
+    for (uint32_t k = 0; mode && k < m; k++)
+        if (!kadstep::full_mode_ok(mode[k])) return fail(err, KAD_ERR_INVALID, "search %u: invalid mode 0x%02x", k, mode[k]);
+    return KAD_OK;
+}
+
 }  // namespace kadplan
+
+extern "C" int kad_search_step_full(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t mode,
+                                    kad_step_full_out* out) {
+    if ((n && !node_flags) || !out || n > 64u || !kadstep::full_mode_ok(mode)) return KAD_ERR_INVALID;
+    kadstep::PlanesFull P;
+    for (uint32_t i = 0; 4u * i < n; i++) {  // the flag bytes four at a time, as the kernel's words hold them
+        uint32_t w = 0;
+        for (uint32_t b = 0; b < 4u && 4u * i + b < n; b++) w |= (uint32_t)node_flags[4u * i + b] << (8u * b);
+        kadstep::add_word_full(P, w, i);
+    }
+    const kadstep::DecisionFull d = kadstep::decide_full(P, n, (search_flags & KAD_SR_EXPIRED) != 0, mode);
+    out->picks = d.picks;
+    out->listen = d.listen;
+    out->announce = d.announce;
+    out->counts = d.counts;
+    out->bits = d.bits;
+    return KAD_OK;
+}
+
+extern "C" int kad_search_step_full_batch(uint32_t m, const uint32_t* off, const uint8_t* node_flags,
+                                          const uint8_t* search_flags, const uint8_t* mode, kad_step_full_out* out) {
+    if (m == 0) return KAD_OK;
+    if (!off || !out || (off[m] && !node_flags)) return KAD_ERR_INVALID;
+    for (uint32_t k = 0; k < m; k++)
+        if (off[k + 1] < off[k] || off[k + 1] - off[k] > 64u || (mode && !kadstep::full_mode_ok(mode[k])))
+            return KAD_ERR_INVALID;
+    for (uint32_t k = 0; k < m; k++)
+        if (int rc = kad_search_step_full(off[k + 1] - off[k], node_flags + off[k], search_flags ? search_flags[k] : 0u,
+                                          mode ? mode[k] : 0u, out + k))
+            return rc;
+    return KAD_OK;
+}
 
 extern "C" int kad_search_step(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t mode,
                                kad_step_out* out) {

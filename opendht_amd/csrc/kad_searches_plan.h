@@ -141,4 +141,12 @@ int sr_entries_plan(uint32_t S, uint32_t p, const uint32_t* pair_which, const ui
 // `err` set.
 int sr_step_check(uint32_t S, uint32_t m, const uint32_t* which, const uint8_t* mode, std::string& err);
 
+// kad_sr_mark_due's plan: sr_entries_plan with the two due bits (0xC0) in place of the four step bits.
+int sr_due_plan(uint32_t S, uint32_t p, const uint32_t* pair_which, const uint8_t* pair_ids, const uint8_t* clear_bits,
+                const uint8_t* set_bits, SrEntriesPlan& out, std::string& err);
+
+// The list checks of kad_sr_step_full: sr_step_check's on m and which, then a byte of mode[0..m) that is not a valid
+// full mode (bit 0x80, DONE_IF_SYNCED with LISTEN or ANNOUNCE, PROBE_BLOCKS without ANNOUNCE).
+int sr_step_full_check(uint32_t S, uint32_t m, const uint32_t* which, const uint8_t* mode, std::string& err);
+
 }  // namespace kadplan

@@ -2,6 +2,8 @@
 // of the member flag bytes, for the host (kad_search_step) and for step_kernel of kad_searches.hip, which call the same
 // functions. Plain C++ without a loop over the entries: popcounts, trailing-zero counts and a fixed number of
 // lowest-bit removals. No HIP call and no header beyond <cstdint>, so the CPU sanitizer build compiles it alone.
+// decide_full adds the listen loop and the announce probes of a synced search over two more planes and
+// hands the get loop to decide; kad_search_step_full and step_full_kernel call it.
 #pragma once
 
 #include <cstdint>
@@ -104,6 +106,70 @@ KAD_STEP_HD Decision decide(Planes P, uint32_t n, bool expired, uint32_t mode) {
     }
     d.counts = n | (n_bad << 8) | (lead << 16) | (solicited << 24);
     return d;
+}
+
+// ---- the whole searchStep: the listen loop (:1384-1428) and the announce probes (:1244-1338) before the get loop, §7.20
+constexpr uint32_t LISTEN_NODES = 4;  // dht.h: the listen loop ends after the fourth synced non-candidate node
+constexpr uint32_t FULL_MODE_BITS = MODE_BITS | KAD_STEP_LISTEN | KAD_STEP_ANNOUNCE | KAD_STEP_PROBE_BLOCKS;
+constexpr uint32_t DUE_BITS = KAD_SN_LISTEN_DUE | KAD_SN_ANNOUNCE_DUE;
+
+// DONE_IF_SYNCED says "no listeners, no announces"; PROBE_BLOCKS speaks of the announce probes
+KAD_STEP_HD bool full_mode_ok(uint32_t mode) {
+    if (mode & ~FULL_MODE_BITS) return false;
+    if ((mode & KAD_STEP_DONE_IF_SYNCED) && (mode & (KAD_STEP_LISTEN | KAD_STEP_ANNOUNCE))) return false;
+    return !(mode & KAD_STEP_PROBE_BLOCKS) || (mode & KAD_STEP_ANNOUNCE);
+}
+
+// Planes with the two due bits beside them
+struct PlanesFull {
+    Planes p;
+    uint64_t ldue = 0, adue = 0;
+};
+
+struct DecisionFull {
+    uint64_t picks, listen, announce;
+    uint32_t counts;  // as Decision; solicited after all three loops
+    uint32_t bits;
+};
+
+KAD_STEP_HD void add_word_full(PlanesFull& P, uint32_t w, uint32_t i) {
+    add_word(P.p, w, i);
+    P.ldue |= gather4(w, 6) << (4u * i);
+    P.adue |= gather4(w, 7) << (4u * i);
+}
+
+// the byte mask that gives entries 4i .. 4i+3 of a flag word `bits` where they are in mask
+KAD_STEP_HD uint32_t mask_bytes(uint64_t mask, uint32_t i, uint32_t bits) {
+    return spread4((uint32_t)(mask >> (4u * i))) * bits;
+}
+
+// Everything up to and including the k-th set bit of v (1 <= k <= 8); all ones if v has fewer than k.
+KAD_STEP_HD uint64_t reach_of(uint64_t v, uint32_t k) {
+    const uint64_t at = drop_lowest(v, k - 1u);  // its lowest bit is the k-th
+    return at ? at ^ (at - 1ull) : ~0ull;
+}
+
+// The step of a list of n <= 64 entries with its listen and announce sends; mode passes full_mode_ok. Bits are read
+// literally: an entry with SYNCED and BAD but without CANDIDATE is the caller's inconsistency and is not repaired.
+KAD_STEP_HD DecisionFull decide_full(PlanesFull F, uint32_t n, bool expired, uint32_t mode) {
+    Planes P = F.p;
+    const uint64_t valid = n >= 64u ? ~0ull : (1ull << n) - 1ull;
+    const uint64_t good = ~P.bad & valid;
+    uint64_t listen = 0ull, announce = 0ull;
+    const uint64_t first = good & ~drop_lowest(good, TARGET_NODES);
+    if (!expired && good && !(first & ~P.sync)) {  // Search::isSynced, as decide has it
+        const uint64_t sync = P.sync & valid;
+        if (mode & KAD_STEP_LISTEN)  // every synced non-candidate counts towards 4, due or not
+            listen = sync & F.ldue & reach_of(sync & ~P.cand, LISTEN_NODES);
+        if (mode & KAD_STEP_ANNOUNCE) {  // only the probed non-candidates count towards 8
+            const uint64_t A = sync & F.adue;
+            announce = A & reach_of(A & ~P.cand, TARGET_NODES);
+        }
+    }
+    P.pend |= announce;  // the probe is a get request: getStatus[probe_query] is pending (:1330)
+    if (mode & KAD_STEP_PROBE_BLOCKS) P.noget |= announce;
+    const Decision d = decide(P, n, expired, mode & MODE_BITS);
+    return {d.picks, listen, announce, d.counts, d.bits};
 }
 
 }  // namespace kadstep

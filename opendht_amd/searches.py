@@ -12,6 +12,8 @@ mark_search_nodes carries the node status changes of a tick (
 every list that holds the node with one kad_sr_mark_nodes, without the host looking for the holders.
 step_searches (DESIGN.md §7.19) is Dht::searchStep's decision on every stepped search with one kad_sr_step: which
 entries get a get request, which searches are synced and which expire, applied to the device set in place.
+step_searches_full is the same with the listen requests and the announce probes of a synced search
+(kad_sr_step_full), for the searches that carry a listen() or a put().
 """
 from __future__ import annotations
 
@@ -22,8 +24,9 @@ import numpy as np
 from ._lib import (KAD_NO_NODE, KAD_SEARCH_NODES, KAD_SN_BAD, KAD_SN_REMOVABLE, KAD_SR_INSERT_OVERFLOW,
                    KAD_SR_REFILL_OVERFLOW, KAD_SR_TICK_APPLIED, KAD_SR_TICK_LEFT,
                    KAD_SR_STOP_END, KAD_SR_STOP_FAR, KAD_SR_STOP_FAR_EXPIRED, KAD_SR_STOP_KNOWN, KAD_STEP_APPLY,
-                   KAD_STEP_DONE, KAD_STEP_EXHAUSTED, KAD_STEP_EXPIRE, KAD_STEP_NO_EXPIRE, KAD_STEP_SHORT,
-                   KAD_STEP_SKIPPED, KAD_STEP_SYNCED, STEP_OUT_DTYPE, check, lib, ptr, sr_step_stats, sr_tick_stats)
+                   KAD_STEP_DONE, KAD_STEP_EXHAUSTED, KAD_STEP_EXPIRE, KAD_STEP_NO_EXPIRE, KAD_STEP_PROBE_BLOCKS,
+                   KAD_STEP_SHORT, KAD_STEP_SKIPPED, KAD_STEP_SYNCED, STEP_FULL_OUT_DTYPE, STEP_OUT_DTYPE, check, lib, ptr,
+                   sr_step_full_stats, sr_step_stats, sr_tick_stats)
 from .table import _as_ids, _stream_of
 
 STOP_NAMES = {KAD_SR_STOP_END: "end", KAD_SR_STOP_KNOWN: "known", KAD_SR_STOP_FAR: "far",
@@ -281,19 +284,7 @@ class DeviceSearches:
         """Step bits of single entries (kad_sr_mark_entries): for every pair (which[k], ids[k]) whose search holds the ID,
         the flag byte becomes (f & ~clear_bits[k]) | set_bits[k] ((p,) uint8 over KAD_SN_CANDIDATE | KAD_SN_PENDING |
         KAD_SN_SYNCED | KAD_SN_NOGET, None for all zero). Returns found (p,) uint8. Synchronous."""
-        pw = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
-        p = pw.shape[0]
-        pid = _as_ids(ids) if p else np.zeros((0, 20), np.uint8)
-        if clear_bits is not None:
-            clear_bits = np.ascontiguousarray(clear_bits, dtype=np.uint8).reshape(-1)
-        if set_bits is not None:
-            set_bits = np.ascontiguousarray(set_bits, dtype=np.uint8).reshape(-1)
-        if pid.shape[0] != p or any(b is not None and b.shape[0] != p for b in (clear_bits, set_bits)):
-            raise ValueError("ids, clear_bits and set_bits must have one entry per pair")
-        found = np.zeros(p, np.uint8)
-        check(lib().kad_sr_mark_entries(self._h, p, ptr(pw), ptr(pid), ptr(clear_bits), ptr(set_bits), ptr(found)),
-              "kad_sr_mark_entries")
-        return found
+        return self._mark_bits("kad_sr_mark_entries", which, ids, clear_bits, set_bits)
 
     def step(self, which=None, modes=None) -> dict:
         """Dht::searchStep's decision on the searches `which` (strictly ascending indices; None: every search) under
@@ -313,6 +304,42 @@ class DeviceSearches:
         out, st = np.zeros(m, STEP_OUT_DTYPE), sr_step_stats()
         check(lib().kad_sr_step(self._h, m, ptr(which), ptr(modes), ptr(out), C.byref(st)), "kad_sr_step")
         return _step_fields(out, {n: getattr(st, n) for n, _ in sr_step_stats._fields_})
+
+    def mark_due(self, which, ids, clear_bits=None, set_bits=None):
+        """mark_entries for the two due bits (kad_sr_mark_due): clear_bits and set_bits over KAD_SN_LISTEN_DUE |
+        KAD_SN_ANNOUNCE_DUE. Returns found (p,) uint8. Synchronous."""
+        return self._mark_bits("kad_sr_mark_due", which, ids, clear_bits, set_bits)
+
+    def _mark_bits(self, call, which, ids, clear_bits, set_bits):
+        pw = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
+        p = pw.shape[0]
+        pid = _as_ids(ids) if p else np.zeros((0, 20), np.uint8)
+        if clear_bits is not None:
+            clear_bits = np.ascontiguousarray(clear_bits, dtype=np.uint8).reshape(-1)
+        if set_bits is not None:
+            set_bits = np.ascontiguousarray(set_bits, dtype=np.uint8).reshape(-1)
+        if pid.shape[0] != p or any(b is not None and b.shape[0] != p for b in (clear_bits, set_bits)):
+            raise ValueError("ids, clear_bits and set_bits must have one entry per pair")
+        found = np.zeros(p, np.uint8)
+        check(getattr(lib(), call)(self._h, p, ptr(pw), ptr(pid), ptr(clear_bits), ptr(set_bits), ptr(found)), call)
+        return found
+
+    def step_full(self, which=None, modes=None) -> dict:
+        """step with the listen and announce sends (kad_sr_step_full): modes may also carry KAD_STEP_LISTEN,
+        KAD_STEP_ANNOUNCE and KAD_STEP_PROBE_BLOCKS. Returns step's arrays plus listen and announce (m,) uint64 (bit e:
+        entry e gets the listen requests due on it / the announce probe); stats is kad_sr_step_full_stats as a dict.
+        With KAD_STEP_APPLY the three kinds of sends and the expiries are written to the set. Synchronous."""
+        if which is not None:
+            which = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
+        m = self.S if which is None else which.shape[0]
+        if modes is not None:
+            modes = (np.full(m, modes, np.uint8) if np.isscalar(modes)
+                     else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1))
+            if modes.shape[0] != m:
+                raise ValueError("modes must have one byte per stepped search")
+        out, st = np.zeros(m, STEP_FULL_OUT_DTYPE), sr_step_full_stats()
+        check(lib().kad_sr_step_full(self._h, m, ptr(which), ptr(modes), ptr(out), C.byref(st)), "kad_sr_step_full")
+        return _step_fields(out, {n: getattr(st, n) for n, _ in sr_step_full_stats._fields_})
 
     @property
     def refill_kernel_ms(self) -> float:
@@ -744,6 +771,8 @@ def _step_fields(out, stats=None) -> dict:
     r = {"picks": out["picks"].copy(), "n": (c & 0xFF).astype(np.uint8), "bad": ((c >> 8) & 0xFF).astype(np.uint8),
          "lead_bad": ((c >> 16) & 0xFF).astype(np.uint8), "solicited": (c >> 24).astype(np.uint8),
          "bits": out["bits"].copy()}
+    if "listen" in (out.dtype.names or ()):
+        r["listen"], r["announce"] = out["listen"].copy(), out["announce"].copy()
     if stats is not None:
         r["stats"] = stats
     return r
@@ -815,6 +844,85 @@ def step_searches(DS, host, which, modes, now) -> dict:
                 out[name].append(s)
         if md[k] & KAD_STEP_APPLY:
             for e in picks:
+                host.send(s, e, now)
+            if bits & KAD_STEP_EXPIRE and not md[k] & KAD_STEP_NO_EXPIRE:
+                host.expire(s)
+    return out
+
+
+def search_step_full(node_flags, search_flags: int = 0, mode: int = 0) -> dict:
+    """search_step with the listen and announce sends (kad_search_step_full): also listen and announce (int masks)."""
+    fl = np.ascontiguousarray(node_flags, dtype=np.uint8).reshape(-1)
+    out = np.zeros(1, STEP_FULL_OUT_DTYPE)
+    rc = lib().kad_search_step_full(fl.shape[0], ptr(fl) if fl.shape[0] else None, search_flags, mode, ptr(out))
+    if rc != 0:
+        raise ValueError(f"kad_search_step_full: {rc}: more than 64 entries or an invalid mode")
+    return {k: int(v[0]) for k, v in _step_fields(out).items()}
+
+
+def search_step_full_batch(off, node_flags, search_flags=None, modes=None) -> dict:
+    """search_step_full on m lists in CSR form, as search_step_batch (kad_search_step_full_batch): the arrays
+    DeviceSearches.step_full returns, without stats."""
+    off = np.ascontiguousarray(off, dtype=np.uint32).reshape(-1)
+    m = off.shape[0] - 1
+    fl = np.ascontiguousarray(node_flags, dtype=np.uint8).reshape(-1)
+    sf = None if search_flags is None else np.ascontiguousarray(search_flags, dtype=np.uint8).reshape(-1)
+    md = None if modes is None else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1)
+    if m < 0 or fl.shape[0] < int(off[-1]) or any(a is not None and a.shape[0] != m for a in (sf, md)):
+        raise ValueError("off needs m + 1 offsets into node_flags, search_flags and modes one byte per list")
+    out = np.zeros(m, STEP_FULL_OUT_DTYPE)
+    rc = lib().kad_search_step_full_batch(m, ptr(off), ptr(fl) if fl.shape[0] else None, ptr(sf), ptr(md), ptr(out))
+    if rc != 0:
+        raise ValueError(f"kad_search_step_full_batch: {rc}: offsets descending, a list of more than 64 entries or an invalid mode")
+    return _step_fields(out)
+
+
+def _positions(mask) -> list:
+    return [e for e in range(64) if (int(mask) >> e) & 1]
+
+
+def step_searches_full(DS, host, which, modes, now) -> dict:
+    """step_searches with the listen requests and announce probes, one kad_sr_step_full. `host` is
+    step_searches' host whose step(s, mode, now) -> (picks, listen, announce, n, bad, lead_bad, solicited, bits) runs all
+    three loops of its own searchStep entry by entry, changing nothing (three lists of positions, in order), and which
+    has beside send(s, pos, now) and expire(s): listen(s, pos, now), the listen requests due on entry pos are sent
+    (listenStatus[query] pending for every listener), and announce_probe(s, pos, now, blocks), the probe to entry pos is
+    sent (getStatus[probe_query] pending; blocks: the mode had KAD_STEP_PROBE_BLOCKS). Every search's device answer is
+    checked against host.step before anything is replayed; a difference raises. For a search whose mode has
+    KAD_STEP_APPLY the listens, the probes and the gets are then replayed in the reference's order, and the expiry
+    unless the mode has KAD_STEP_NO_EXPIRE.
+
+    Returns step_searches' dict plus "listen" and "announce" ({search: list positions})."""
+    idx = np.arange(DS.S, dtype=np.uint32) if which is None else np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
+    m = idx.shape[0]
+    md = np.zeros(m, np.uint8) if modes is None else (np.full(m, modes, np.uint8) if np.isscalar(modes)
+                                                      else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1))
+    want = [host.step(int(s), int(md[k]), now) for k, s in enumerate(idx)]
+    r = DS.step_full(which, md)
+    out = {"synced": [], "short": [], "done": [], "exhausted": [], "expire": [], "skipped": [], "picks": {},
+           "listen": {}, "announce": {}, "stats": r["stats"]}
+    names = ((KAD_STEP_SYNCED, "synced"), (KAD_STEP_SHORT, "short"), (KAD_STEP_DONE, "done"),
+             (KAD_STEP_EXHAUSTED, "exhausted"), (KAD_STEP_EXPIRE, "expire"), (KAD_STEP_SKIPPED, "skipped"))
+    for k, s in enumerate(idx):
+        got = (_positions(r["picks"][k]), _positions(r["listen"][k]), _positions(r["announce"][k]), int(r["n"][k]),
+               int(r["bad"][k]), int(r["lead_bad"][k]), int(r["solicited"][k]), int(r["bits"][k]))
+        w = want[k]
+        if got != tuple(list(v) for v in w[:3]) + tuple(int(v) for v in w[3:]):
+            raise RuntimeError(f"step_searches_full: search {int(s)} stepped to {w} on the host, {got} on the device")
+    for k, s in enumerate(idx):
+        s, bits = int(s), int(r["bits"][k])
+        for name, pos in zip(("picks", "listen", "announce"), want[k][:3]):
+            if pos:
+                out[name][s] = list(pos)
+        for bit, name in names:
+            if bits & bit:
+                out[name].append(s)
+        if md[k] & KAD_STEP_APPLY:
+            for e in want[k][1]:
+                host.listen(s, e, now)
+            for e in want[k][2]:
+                host.announce_probe(s, e, now, bool(md[k] & KAD_STEP_PROBE_BLOCKS))
+            for e in want[k][0]:
                 host.send(s, e, now)
             if bits & KAD_STEP_EXPIRE and not md[k] & KAD_STEP_NO_EXPIRE:
                 host.expire(s)
