@@ -1345,36 +1345,12 @@ public:
                                                               const std::vector<uint8_t>& modes = std::vector<uint8_t>()) {
         std::vector<SteppedSearch<InfoHashT, NodePtrT>> out(ids.size());
         if (ids.empty()) return out;
-        if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatch before snapshot");
-        if (!modes.empty() && modes.size() != ids.size())
-            throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatch: one mode per search, or none");
-        std::vector<std::pair<uint32_t, size_t>> order(ids.size());  // (search index, position in ids), ascending
-        for (size_t k = 0; k < ids.size(); k++) order[k] = std::make_pair(index_of(id_bytes(ids[k])), k);
-        std::sort(order.begin(), order.end());
-        std::vector<uint32_t> which(ids.size());
-        std::vector<uint8_t> md(ids.size(), 0);
-        for (size_t k = 0; k < order.size(); k++) {
-            if (k && order[k].first == order[k - 1].first)
-                throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatch: a search listed twice");
-            which[k] = order[k].first;
-            if (!modes.empty()) md[k] = modes[order[k].second];
-        }
         std::vector<kad_step_out> res(ids.size());
-        check(kad_sr_step(ss_, (uint32_t)which.size(), which.data(), md.data(), res.data(), nullptr), "kad_sr_step");
-        for (size_t k = 0; k < order.size(); k++) {
+        const auto order = stepCall("SearchesMirror::stepBatch", &kad_sr_step, "kad_sr_step", ids, modes, res);
+        for (size_t k = 0; k < res.size(); k++) {
             SteppedSearch<InfoHashT, NodePtrT>& o = out[order[k].second];
-            const auto it = map_->find(ids[order[k].second]);
-            if (it == map_->end()) throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
-            o.id = it->first;
-            o.n = (uint8_t)res[k].counts;
-            o.bad = (uint8_t)(res[k].counts >> 8);
-            o.lead_bad = (uint8_t)(res[k].counts >> 16);
-            o.solicited = (uint8_t)(res[k].counts >> 24);
-            o.bits = res[k].bits;
-            if (o.n != it->second->nodes.size())
-                throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatch: the host's list differs from the mirrored one (sync it)");
-            for (uint32_t e = 0; e < o.n; e++)
-                if ((res[k].picks >> e) & 1ull) o.picks.push_back(it->second->nodes[e].node);
+            const auto it = stepped("SearchesMirror::stepBatch", ids[order[k].second], res[k].counts, res[k].bits, o);
+            pickNodes(it->second->nodes, res[k].picks, o.n, o.picks);
         }
         return out;
     }
@@ -1403,44 +1379,66 @@ public:
         const std::vector<InfoHashT>& ids, const std::vector<uint8_t>& modes = std::vector<uint8_t>()) {
         std::vector<FullySteppedSearch<InfoHashT, NodePtrT>> out(ids.size());
         if (ids.empty()) return out;
-        if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatchFull before snapshot");
-        if (!modes.empty() && modes.size() != ids.size())
-            throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatchFull: one mode per search, or none");
-        std::vector<std::pair<uint32_t, size_t>> order(ids.size());  // (search index, position in ids), ascending
-        for (size_t k = 0; k < ids.size(); k++) order[k] = std::make_pair(index_of(id_bytes(ids[k])), k);
-        std::sort(order.begin(), order.end());
-        std::vector<uint32_t> which(ids.size());
-        std::vector<uint8_t> md(ids.size(), 0);
-        for (size_t k = 0; k < order.size(); k++) {
-            if (k && order[k].first == order[k - 1].first)
-                throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatchFull: a search listed twice");
-            which[k] = order[k].first;
-            if (!modes.empty()) md[k] = modes[order[k].second];
-        }
         std::vector<kad_step_full_out> res(ids.size());
-        check(kad_sr_step_full(ss_, (uint32_t)which.size(), which.data(), md.data(), res.data(), nullptr), "kad_sr_step_full");
-        for (size_t k = 0; k < order.size(); k++) {
+        const auto order = stepCall("SearchesMirror::stepBatchFull", &kad_sr_step_full, "kad_sr_step_full", ids, modes, res);
+        for (size_t k = 0; k < res.size(); k++) {
             FullySteppedSearch<InfoHashT, NodePtrT>& o = out[order[k].second];
-            const auto it = map_->find(ids[order[k].second]);
-            if (it == map_->end()) throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
-            o.id = it->first;
-            o.n = (uint8_t)res[k].counts;
-            o.bad = (uint8_t)(res[k].counts >> 8);
-            o.lead_bad = (uint8_t)(res[k].counts >> 16);
-            o.solicited = (uint8_t)(res[k].counts >> 24);
-            o.bits = res[k].bits;
-            if (o.n != it->second->nodes.size())
-                throw Error(KAD_ERR_INVALID, "SearchesMirror::stepBatchFull: the host's list differs from the mirrored one (sync it)");
-            for (uint32_t e = 0; e < o.n; e++) {
-                if ((res[k].picks >> e) & 1ull) o.picks.push_back(it->second->nodes[e].node);
-                if ((res[k].listen >> e) & 1ull) o.listen.push_back(it->second->nodes[e].node);
-                if ((res[k].announce >> e) & 1ull) o.announce.push_back(it->second->nodes[e].node);
-            }
+            const auto it = stepped("SearchesMirror::stepBatchFull", ids[order[k].second], res[k].counts, res[k].bits, o);
+            pickNodes(it->second->nodes, res[k].picks, o.n, o.picks);
+            pickNodes(it->second->nodes, res[k].listen, o.n, o.listen);
+            pickNodes(it->second->nodes, res[k].announce, o.n, o.announce);
         }
         return out;
     }
 
 private:
+    /* stepBatch's and stepBatchFull's (`who`) searches as `call` (kad_sr_step, kad_sr_step_full: `what`) takes them,
+     * and the call: returns (search index, position in ids) ascending; res[k] answers the k-th of them. */
+    template <class InfoHashT, class OutT, class StatsT>
+    std::vector<std::pair<uint32_t, size_t>> stepCall(
+        const std::string& who, int (*call)(kad_searches*, uint32_t, const uint32_t*, const uint8_t*, OutT*, StatsT*),
+        const char* what, const std::vector<InfoHashT>& ids, const std::vector<uint8_t>& modes, std::vector<OutT>& res) {
+        if (!ss_) throw Error(KAD_ERR_INVALID, who + " before snapshot");
+        if (!modes.empty() && modes.size() != ids.size()) throw Error(KAD_ERR_INVALID, who + ": one mode per search, or none");
+        std::vector<std::pair<uint32_t, size_t>> order(ids.size());
+        for (size_t k = 0; k < ids.size(); k++) order[k] = std::make_pair(index_of(id_bytes(ids[k])), k);
+        std::sort(order.begin(), order.end());
+        std::vector<uint32_t> which(ids.size());
+        std::vector<uint8_t> md(ids.size(), 0);
+        for (size_t k = 0; k < order.size(); k++) {
+            if (k && order[k].first == order[k - 1].first) throw Error(KAD_ERR_INVALID, who + ": a search listed twice");
+            which[k] = order[k].first;
+            if (!modes.empty()) md[k] = modes[order[k].second];
+        }
+        check(call(ss_, (uint32_t)which.size(), which.data(), md.data(), res.data(), nullptr), what);
+        return order;
+    }
+
+    /* The fields every stepped search has, from the device's counts and bits. Returns the host's search, whose list
+     * must be as long as the device's. */
+    template <class InfoHashT, class ResultT, class MapT = SearchMapT>
+    typename MapT::const_iterator stepped(const std::string& who, const InfoHashT& id, uint32_t counts, uint32_t bits,
+                                          ResultT& o) {
+        const auto it = map_->find(id);
+        if (it == map_->end()) throw Error(KAD_ERR_INVALID, "the search map changed its keys (snapshot again)");
+        o.id = it->first;
+        o.n = (uint8_t)counts;
+        o.bad = (uint8_t)(counts >> 8);
+        o.lead_bad = (uint8_t)(counts >> 16);
+        o.solicited = (uint8_t)(counts >> 24);
+        o.bits = bits;
+        if (o.n != it->second->nodes.size())
+            throw Error(KAD_ERR_INVALID, who + ": the host's list differs from the mirrored one (sync it)");
+        return it;
+    }
+
+    /* the nodes at the list positions below n that mask names, in list order */
+    template <class NodesT, class NodePtrT>
+    static void pickNodes(const NodesT& nodes, uint64_t mask, uint32_t n, std::vector<NodePtrT>& out) {
+        for (uint32_t e = 0; e < n; e++)
+            if ((mask >> e) & 1ull) out.push_back(nodes[e].node);
+    }
+
     template <class InfoHashT, class When>
     void syncAt(const std::vector<InfoHashT>& changed, const When& when) {
         if (!ss_) throw Error(KAD_ERR_INVALID, "SearchesMirror::sync before snapshot");

@@ -43,7 +43,8 @@
 //
 // kad_sr_step_full is the same step with the two send loops that precede the get loop: the listen
 // requests and the announce probes of a synced search, from two more bits of the flag byte (kad_sr_mark_due sets them).
-// step_full_kernel is step_kernel's shape over seven planes and kadstep::decide_full; step_expire_kernel is shared.
+// step_full_kernel and step_kernel are one body (step_lane), here over seven planes and kadstep::decide_full, and the two
+// calls are one host body (step_call); step_expire_kernel is shared.
 //
 // kad_searches_apply changes the membership (Dht::search dht.cpp:1673-1735, Dht::expireSearches
 // :1060-1074) and the slab size: the host plans one source word per new search, searches_relayout_kernel gathers the
@@ -133,6 +134,50 @@ struct DeviceGuard {
         if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
     }
 };
+
+// What a call that changes the set holds while it runs: the set's device made current, the call's one device allocation
+// and its host staging buffer (a new[] array handed over, or none), both released when the scope ends.
+struct CallScratch {
+    DeviceGuard g;
+    uint8_t* buf = nullptr;
+    uint8_t* h;
+    explicit CallScratch(int dev, uint8_t* host = nullptr) : g(dev), h(host) {}
+    CallScratch(const CallScratch&) = delete;
+    CallScratch& operator=(const CallScratch&) = delete;
+    ~CallScratch() {
+        if (buf) (void)hipFree(buf);
+        delete[] h;
+    }
+    // Waits for everything enqueued before the call (queries enqueued before it read the old set), then allocates
+    // `bytes` of device memory. KAD_OK, or the error set with `what` as its prefix.
+    int open(size_t bytes, const char* what) {
+        if (hipDeviceSynchronize() != hipSuccess)
+            return set_error(KAD_ERR_HIP, (std::string(what) + ": device in error").c_str());
+        if (hipMalloc((void**)&buf, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            buf = nullptr;
+            return set_error(KAD_ERR_NOMEM, (std::string(what) + ": out of device memory").c_str());
+        }
+        return KAD_OK;
+    }
+};
+
+// the handle's timing events, created by the first call that needs them
+template <size_t N>
+bool have_events(hipEvent_t (&ev)[N]) {
+    for (hipEvent_t& e : ev)
+        if (!e && hipEventCreate(&e) != hipSuccess) return false;
+    return true;
+}
+
+float elapsed_or_zero(hipEvent_t ev0, hipEvent_t ev1) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ev0, ev1) != hipSuccess) {
+        (void)hipGetLastError();
+        ms = 0.f;
+    }
+    return ms;
+}
 
 struct DevSearches {
     const u32x4_t* rec;
@@ -1037,10 +1082,10 @@ __global__ __launch_bounds__(BLOCK) void entries_kernel(DevEntries D) {
     }
 }
 
-// One lane per stepped search: n and the expired bit from the record, the flag bytes of the entries below n as words
-// (WIDE, cap a multiple of 16: every slab starts on a 16-byte boundary and is read as 16-byte units; otherwise byte by
-// byte, as a slab then starts anywhere), the words turned into kadstep's five planes, kadstep::decide, one 16-byte store.
-// With KAD_STEP_APPLY the flag units that hold a picked entry are stored back with PENDING | NOGET on it; a search that
+// One lane per stepped search, step_kernel and step_full_kernel alike (step_lane): n and the expired bit from the record,
+// the flag bytes of the entries below n as words (WIDE, cap a multiple of 16: every slab starts on a 16-byte boundary and
+// is read as 16-byte units; otherwise byte by byte, as a slab then starts anywhere), the words turned into kadstep's
+// planes, the decision, the result stored. With KAD_STEP_APPLY the entries a loop sent to are rewritten; a search that
 // expires is appended to a list instead, and step_expire_kernel empties it.
 struct DevStep {
     uint32_t* rec;
@@ -1050,22 +1095,14 @@ struct DevStep {
     uint32_t S, cap, m;
     const uint32_t* which;  // m, NULL: search i
     const uint8_t* mode;    // m, NULL: all zero
-    u32x4_t* out;           // m
-    uint32_t* n_exp;        // the number of searches to expire, and the searches: room for m
+    u32x4_t* out;           // m units, 2 m for step_full_kernel
+    uint32_t* n_exp;      // the number of searches to expire, and the searches: room for m
     uint32_t* exp_list;
 };
 
+// the flag bytes of entries 4k .. 4k+3 in w[k]; zero from n on (the slab's padding is zero)
 template <bool WIDE>
-__global__ __launch_bounds__(BLOCK) void step_kernel(DevStep D) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= D.m) return;
-    const uint32_t s = D.which ? min(D.which[i], D.S - 1u) : i;
-    const uint32_t mode = D.mode ? (uint32_t)D.mode[i] : 0u;
-    const uint32_t* r = D.rec + (uint64_t)SREC_WORDS * s;
-    const uint32_t n = min(r[SREC_N], D.cap);
-    const bool expired = (r[SREC_BITS] & SREC_EXPIRED) != 0;
-    uint8_t* fl = D.mflag + (uint64_t)s * D.cap;
-    uint32_t w[16];  // the flag bytes of entries 4k .. 4k+3; zero from n on (the slab's padding is zero)
+__device__ __forceinline__ void load_flag_words(const uint8_t* fl, uint32_t n, uint32_t (&w)[16]) {
     if (WIDE) {
         const u32x4_t* fu = reinterpret_cast<const u32x4_t*>(fl);
 #pragma unroll
@@ -1087,38 +1124,95 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(DevStep D) {
             w[k] = v;
         }
     }
-    kadstep::Planes P;
+}
+
+// the bytes of v stored back for the entries in `touched` (all below n): WIDE the 16-byte units that hold one, otherwise
+// those bytes alone
+template <bool WIDE>
+__device__ __forceinline__ void store_flag_words(uint8_t* fl, uint64_t touched, const uint32_t (&v)[16]) {
+    if (WIDE) {
+        u32x4_t* fu = reinterpret_cast<u32x4_t*>(fl);
 #pragma unroll
-    for (uint32_t k = 0; k < 16; k++) kadstep::add_word(P, w[k], k);
-    const kadstep::Decision d = kadstep::decide(P, n, expired, mode);
-    if (mode & KAD_STEP_APPLY) {
-        if ((d.bits & KAD_STEP_EXPIRE) && !(mode & KAD_STEP_NO_EXPIRE)) {
-            D.exp_list[min(atomicAdd(D.n_exp, 1u), D.m - 1u)] = s;
-        } else if (d.picks) {  // picks lie below n
-            if (WIDE) {
-                u32x4_t* fu = reinterpret_cast<u32x4_t*>(fl);
-#pragma unroll
-                for (uint32_t k = 0; k < 4; k++) {
-                    const u32x4_t a = {kadstep::sent_bytes(d.picks, 4 * k), kadstep::sent_bytes(d.picks, 4 * k + 1),
-                                       kadstep::sent_bytes(d.picks, 4 * k + 2), kadstep::sent_bytes(d.picks, 4 * k + 3)};
-                    if ((d.picks >> (16u * k)) & 0xFFFFull) {
-                        const u32x4_t v = {w[4 * k] | a.x, w[4 * k + 1] | a.y, w[4 * k + 2] | a.z, w[4 * k + 3] | a.w};
-                        fu[k] = v;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (uint32_t k = 0; k < 16; k++) {
-                    const uint32_t v = w[k] | kadstep::sent_bytes(d.picks, k);
-#pragma unroll
-                    for (uint32_t b = 0; b < 4; b++)
-                        if ((d.picks >> (4u * k + b)) & 1ull) fl[4u * k + b] = (uint8_t)(v >> (8u * b));
-                }
+        for (uint32_t k = 0; k < 4; k++) {
+            if ((touched >> (16u * k)) & 0xFFFFull) {
+                const u32x4_t u = {v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]};
+                fu[k] = u;
             }
         }
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < 16; k++) {
+#pragma unroll
+            for (uint32_t b = 0; b < 4; b++)
+                if ((touched >> (4u * k + b)) & 1ull) fl[4u * k + b] = (uint8_t)(v[k] >> (8u * b));
+        }
     }
-    const u32x4_t o = {(uint32_t)d.picks, (uint32_t)(d.picks >> 32), d.counts, d.bits};
-    __builtin_nontemporal_store(o, D.out + i);
+}
+
+// FULL (kad_sr_step_full): all eight bits of the flag bytes as kadstep's seven planes, decide_full's three
+// send loops, a 32-byte result as two 16-byte stores (D.out holds 2 m units). Otherwise (kad_sr_step, §7.19) five planes,
+// decide's get loop and one 16-byte store. With KAD_STEP_APPLY an entry picked by any loop is rewritten: PENDING for a get
+// request or a probe, NOGET for a get request (and for a probe under PROBE_BLOCKS), LISTEN_DUE and ANNOUNCE_DUE cleared
+// where that loop sent. Without listens and probes that is PENDING | NOGET on the picks.
+template <bool WIDE, bool FULL>
+__device__ __forceinline__ void step_lane(const DevStep& D) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= D.m) return;
+    const uint32_t s = D.which ? min(D.which[i], D.S - 1u) : i;
+    const uint32_t mode = D.mode ? (uint32_t)D.mode[i] : 0u;
+    const uint32_t* r = D.rec + (uint64_t)SREC_WORDS * s;
+    const uint32_t n = min(r[SREC_N], D.cap);
+    const bool expired = (r[SREC_BITS] & SREC_EXPIRED) != 0;
+    uint8_t* fl = D.mflag + (uint64_t)s * D.cap;
+    uint32_t w[16];
+    load_flag_words<WIDE>(fl, n, w);
+    kadstep::DecisionFull d;
+    if (FULL) {
+        kadstep::PlanesFull P;
+#pragma unroll
+        for (uint32_t k = 0; k < 16; k++) kadstep::add_word_full(P, w[k], k);
+        d = kadstep::decide_full(P, n, expired, mode);
+    } else {
+        kadstep::Planes P;
+#pragma unroll
+        for (uint32_t k = 0; k < 16; k++) kadstep::add_word(P, w[k], k);
+        const kadstep::Decision g = kadstep::decide(P, n, expired, mode);
+        d = {g.picks, 0ull, 0ull, g.counts, g.bits};
+    }
+    if (mode & KAD_STEP_APPLY) {
+        const uint64_t pend = d.picks | d.announce, noget = d.picks | ((mode & KAD_STEP_PROBE_BLOCKS) ? d.announce : 0ull);
+        const uint64_t touched = pend | d.listen;  // all below n
+        if ((d.bits & KAD_STEP_EXPIRE) && !(mode & KAD_STEP_NO_EXPIRE)) {
+            D.exp_list[min(atomicAdd(D.n_exp, 1u), D.m - 1u)] = s;
+        } else if (touched) {
+            uint32_t v[16];
+#pragma unroll
+            for (uint32_t k = 0; k < 16; k++)
+                v[k] = (w[k] | kadstep::mask_bytes(pend, k, KAD_SN_PENDING) | kadstep::mask_bytes(noget, k, KAD_SN_NOGET)) &
+                       ~kadstep::mask_bytes(d.listen, k, KAD_SN_LISTEN_DUE) &
+                       ~kadstep::mask_bytes(d.announce, k, KAD_SN_ANNOUNCE_DUE);
+            store_flag_words<WIDE>(fl, touched, v);
+        }
+    }
+    if (FULL) {
+        const u32x4_t o0 = {(uint32_t)d.picks, (uint32_t)(d.picks >> 32), (uint32_t)d.listen, (uint32_t)(d.listen >> 32)};
+        const u32x4_t o1 = {(uint32_t)d.announce, (uint32_t)(d.announce >> 32), d.counts, d.bits};
+        __builtin_nontemporal_store(o0, D.out + 2ull * i);
+        __builtin_nontemporal_store(o1, D.out + 2ull * i + 1ull);
+    } else {
+        const u32x4_t o = {(uint32_t)d.picks, (uint32_t)(d.picks >> 32), d.counts, d.bits};
+        __builtin_nontemporal_store(o, D.out + i);
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(BLOCK) void step_kernel(DevStep D) {
+    step_lane<WIDE, false>(D);
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(BLOCK) void step_full_kernel(DevStep D) {
+    step_lane<WIDE, true>(D);
 }
 
 // Search::expire() (dht.cpp:649-653) on the listed searches, one wave per search: the slab all zero and the record's
@@ -1143,82 +1237,73 @@ __global__ __launch_bounds__(BLOCK) void step_expire_kernel(DevStep D) {
     }
 }
 
-// kad_sr_step_full: step_kernel's lane, loads and stores over all eight bits of the flag bytes. The
-// words become kadstep's seven planes, kadstep::decide_full answers the three send loops, and the 32-byte result goes out
-// as two 16-byte stores (D.out holds 2 m units). With KAD_STEP_APPLY an entry picked by any loop is rewritten: PENDING for
-// a get request or a probe, NOGET for a get request (and for a probe under PROBE_BLOCKS), LISTEN_DUE and ANNOUNCE_DUE
-// cleared where that loop sent; only the units that hold such an entry are stored back.
-template <bool WIDE>
-__global__ __launch_bounds__(BLOCK) void step_full_kernel(DevStep D) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= D.m) return;
-    const uint32_t s = D.which ? min(D.which[i], D.S - 1u) : i;
-    const uint32_t mode = D.mode ? (uint32_t)D.mode[i] : 0u;
-    const uint32_t* r = D.rec + (uint64_t)SREC_WORDS * s;
-    const uint32_t n = min(r[SREC_N], D.cap);
-    const bool expired = (r[SREC_BITS] & SREC_EXPIRED) != 0;
-    uint8_t* fl = D.mflag + (uint64_t)s * D.cap;
-    uint32_t w[16];  // the flag bytes of entries 4k .. 4k+3; zero from n on (the slab's padding is zero)
-    if (WIDE) {
-        const u32x4_t* fu = reinterpret_cast<const u32x4_t*>(fl);
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++) {
-            u32x4_t u = {0u, 0u, 0u, 0u};
-            if (16u * k < n) u = fu[k];
-            w[4 * k] = u.x;
-            w[4 * k + 1] = u.y;
-            w[4 * k + 2] = u.z;
-            w[4 * k + 3] = u.w;
-        }
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < 16; k++) {
-            uint32_t v = 0;
-#pragma unroll
-            for (uint32_t b = 0; b < 4; b++)
-                if (4u * k + b < n) v |= (uint32_t)fl[4u * k + b] << (8u * b);
-            w[k] = v;
-        }
+// kad_sr_step (Out = kad_step_out, 16 bytes a search) and kad_sr_step_full (kad_step_full_out, 32 bytes): the checks of
+// `check`, the call's scratch, the step kernel of Out's width, the expire pass, the copy back and the counts of Stats.
+// `what` opens every message; `unsupported` is the whole text for slabs of more than 64 entries.
+template <class Out, class Stats>
+int step_call(kad_searches* ss, uint32_t m, const uint32_t* which, const uint8_t* mode, Out* out, Stats* out_stats,
+              int (*check)(uint32_t, uint32_t, const uint32_t*, const uint8_t*, std::string&), const char* what,
+              const char* unsupported) {
+    constexpr bool FULL = sizeof(Out) == 32;
+    static_assert(sizeof(Out) == (FULL ? 32 : 16), "one 16-byte store per search, or two");
+    if (!ss || !out) return set_error(KAD_ERR_INVALID, "NULL search set or output");
+    std::string err;
+    if (int rc = check(ss->S, m, which, mode, err)) return set_error(rc, err.c_str());
+    Stats st = {};
+    if (m == 0) {
+        if (out_stats) *out_stats = st;
+        return KAD_OK;
     }
-    kadstep::PlanesFull P;
-#pragma unroll
-    for (uint32_t k = 0; k < 16; k++) kadstep::add_word_full(P, w[k], k);
-    const kadstep::DecisionFull d = kadstep::decide_full(P, n, expired, mode);
-    if (mode & KAD_STEP_APPLY) {
-        const uint64_t pend = d.picks | d.announce, noget = d.picks | ((mode & KAD_STEP_PROBE_BLOCKS) ? d.announce : 0ull);
-        const uint64_t touched = pend | d.listen;  // all below n
-        if ((d.bits & KAD_STEP_EXPIRE) && !(mode & KAD_STEP_NO_EXPIRE)) {
-            D.exp_list[min(atomicAdd(D.n_exp, 1u), D.m - 1u)] = s;
-        } else if (touched) {
-            uint32_t v[16];
-#pragma unroll
-            for (uint32_t k = 0; k < 16; k++)
-                v[k] = (w[k] | kadstep::mask_bytes(pend, k, KAD_SN_PENDING) | kadstep::mask_bytes(noget, k, KAD_SN_NOGET)) &
-                       ~kadstep::mask_bytes(d.listen, k, KAD_SN_LISTEN_DUE) &
-                       ~kadstep::mask_bytes(d.announce, k, KAD_SN_ANNOUNCE_DUE);
-            if (WIDE) {
-                u32x4_t* fu = reinterpret_cast<u32x4_t*>(fl);
-#pragma unroll
-                for (uint32_t k = 0; k < 4; k++) {
-                    if ((touched >> (16u * k)) & 0xFFFFull) {
-                        const u32x4_t u = {v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]};
-                        fu[k] = u;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (uint32_t k = 0; k < 16; k++) {
-#pragma unroll
-                    for (uint32_t b = 0; b < 4; b++)
-                        if ((touched >> (4u * k + b)) & 1ull) fl[4u * k + b] = (uint8_t)(v[k] >> (8u * b));
-                }
+    if (ss->cap > REFILL_MAX_CAP) return set_error(KAD_ERR_UNSUPPORTED, unsupported);
+    bool any_apply = false;
+    for (uint32_t k = 0; mode && k < m && !any_apply; k++) any_apply = (mode[k] & KAD_STEP_APPLY) != 0;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    auto msg = [what](const char* text) { return std::string(what) + ": " + text; };
+    // the call's scratch, one allocation: the listed searches and the modes (one upload each, when given), the results
+    // (one copy back), the count of searches to expire and their list
+    const size_t o_mode = which ? 4ull * m : 0, o_out = up16(o_mode + (mode ? m : 0)), o_head = o_out + sizeof(Out) * m,
+                 o_list = o_head + 16, total = o_list + 4ull * m;
+    CallScratch cs(ss->device);
+    if (int rc = cs.open(total, what)) return rc;
+    uint8_t* const buf = cs.buf;
+    if (!have_events(ss->sp_ev)) return set_error(KAD_ERR_HIP, msg("no events").c_str());
+    if ((which && hipMemcpy(buf, which, 4ull * m, hipMemcpyHostToDevice) != hipSuccess) ||
+        (mode && hipMemcpy(buf + o_mode, mode, m, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemsetAsync(buf + o_head, 0, 16, nullptr) != hipSuccess)
+        return set_error(KAD_ERR_HIP, msg("H2D failed").c_str());
+    const DevStep D{ss->rec, ss->mkey, ss->mtail, ss->mflag, ss->S, ss->cap, m,
+                    which ? (const uint32_t*)buf : nullptr, mode ? buf + o_mode : nullptr, (u32x4_t*)(buf + o_out),
+                    (uint32_t*)(buf + o_head), (uint32_t*)(buf + o_list)};
+    const bool wide = ss->cap % 16 == 0;
+    void (*const kernel)(DevStep) = FULL ? (wide ? step_full_kernel<true> : step_full_kernel<false>)
+                                         : (wide ? step_kernel<true> : step_kernel<false>);
+    (void)hipEventRecord(ss->sp_ev[0], nullptr);
+    hipLaunchKernelGGL(kernel, dim3((m + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, D);
+    hipError_t le = hipGetLastError();
+    if (le == hipSuccess && any_apply) {  // the grid is sized without the count: the waves stride over what the head says
+        const uint32_t blocks = (m + REFILL_WAVES - 1) / REFILL_WAVES, grid = blocks < MARK_FIX_GRID ? blocks : MARK_FIX_GRID;
+        hipLaunchKernelGGL(step_expire_kernel, dim3(grid), dim3(BLOCK), 0, nullptr, D);
+        le = hipGetLastError();
+    }
+    (void)hipEventRecord(ss->sp_ev[1], nullptr);
+    if (le != hipSuccess) return set_error(KAD_ERR_HIP, (msg("launch failed: ") + hipGetErrorString(le)).c_str());
+    const hipError_t ce = hipMemcpy(out, buf + o_out, sizeof(Out) * m, hipMemcpyDeviceToHost);
+    if (ce != hipSuccess) return set_error(KAD_ERR_HIP, (msg("D2H failed: ") + hipGetErrorString(ce)).c_str());
+    st.kernel_ms = elapsed_or_zero(ss->sp_ev[0], ss->sp_ev[1]);
+    if (out_stats) {
+        for (uint32_t k = 0; k < m; k++) {
+            st.synced += (out[k].bits & KAD_STEP_SYNCED) ? 1u : 0u;
+            st.expired += (out[k].bits & KAD_STEP_EXPIRE) ? 1u : 0u;
+            st.skipped += (out[k].bits & KAD_STEP_SKIPPED) ? 1u : 0u;
+            st.picks += (uint32_t)__builtin_popcountll(out[k].picks);
+            if constexpr (FULL) {
+                st.listens += (uint32_t)__builtin_popcountll(out[k].listen);
+                st.announces += (uint32_t)__builtin_popcountll(out[k].announce);
             }
         }
+        *out_stats = st;
     }
-    const u32x4_t o0 = {(uint32_t)d.picks, (uint32_t)(d.picks >> 32), (uint32_t)d.listen, (uint32_t)(d.listen >> 32)};
-    const u32x4_t o1 = {(uint32_t)d.announce, (uint32_t)(d.announce >> 32), d.counts, d.bits};
-    __builtin_nontemporal_store(o0, D.out + 2ull * i);
-    __builtin_nontemporal_store(o1, D.out + 2ull * i + 1ull);
+    return KAD_OK;
 }
 
 // ---- kad_searches_apply: add and erase searches, grow the slabs -----------------------------------
@@ -1725,8 +1810,7 @@ int kad_sr_refill(kad_searches* ss, const kad_table* nc, uint32_t m, const uint3
         delete[] h;
         return r;
     };
-    if (!ss->rf_ev[0] && (hipEventCreate(&ss->rf_ev[0]) != hipSuccess || hipEventCreate(&ss->rf_ev[1]) != hipSuccess))
-        return done(set_error(KAD_ERR_HIP, "refill: no events"));
+    if (!have_events(ss->rf_ev)) return done(set_error(KAD_ERR_HIP, "refill: no events"));
     if (hipMemcpy(buf, which, 4ull * m, hipMemcpyHostToDevice) != hipSuccess)
         return done(set_error(KAD_ERR_HIP, "refill: H2D failed"));
     uint32_t* d_which = (uint32_t*)buf;
@@ -1746,10 +1830,7 @@ int kad_sr_refill(kad_searches* ss, const kad_table* nc, uint32_t m, const uint3
     const hipError_t ce = hipMemcpy(h, buf + o_back, total - o_back, hipMemcpyDeviceToHost);
     if (ce != hipSuccess)
         return done(set_error(KAD_ERR_HIP, (std::string("refill: D2H failed: ") + hipGetErrorString(ce)).c_str()));
-    if (hipEventElapsedTime(&ss->rf_ms, ss->rf_ev[0], ss->rf_ev[1]) != hipSuccess) {
-        (void)hipGetLastError();
-        ss->rf_ms = 0.f;
-    }
+    ss->rf_ms = elapsed_or_zero(ss->rf_ev[0], ss->rf_ev[1]);
     if (out_rows) std::memcpy(out_rows, h, o_ins - o_rows);
     std::memcpy(out_inserted, h + (o_ins - o_back), 2ull * m);
     std::memcpy(out_cnt, h + (o_cnt - o_back), m);
@@ -1787,24 +1868,12 @@ int kad_sr_insert(kad_searches* ss, uint32_t m, const uint32_t* which, const uin
         std::memcpy(h + o_fl, cand_flags, T);
     else
         std::memset(h + o_fl, 0, T);
-    DeviceGuard g(ss->device);
-    uint8_t* buf = nullptr;
-    auto done = [&](int r) {
-        if (buf) (void)hipFree(buf);
-        delete[] h;
-        return r;
-    };
-    if (hipDeviceSynchronize() != hipSuccess)  // queries enqueued before the call read the old set
-        return done(set_error(KAD_ERR_HIP, "insert: device in error"));
-    if (hipMalloc((void**)&buf, total) != hipSuccess) {
-        (void)hipGetLastError();
-        buf = nullptr;
-        return done(set_error(KAD_ERR_NOMEM, "insert: out of device memory"));
-    }
-    if (!ss->in_ev[0] && (hipEventCreate(&ss->in_ev[0]) != hipSuccess || hipEventCreate(&ss->in_ev[1]) != hipSuccess))
-        return done(set_error(KAD_ERR_HIP, "insert: no events"));
+    CallScratch cs(ss->device, h);
+    if (int rc = cs.open(total, "insert")) return rc;
+    uint8_t* const buf = cs.buf;
+    if (!have_events(ss->in_ev)) return set_error(KAD_ERR_HIP, "insert: no events");
     if (hipMemcpy(buf, h, o_ins, hipMemcpyHostToDevice) != hipSuccess)
-        return done(set_error(KAD_ERR_HIP, "insert: H2D failed"));
+        return set_error(KAD_ERR_HIP, "insert: H2D failed");
     const DevInsert D{ss->rec, ss->mkey, ss->mtail, ss->mflag, ss->cap, m, (const uint32_t*)buf,
                       (const uint32_t*)(buf + o_off), buf + o_ids, buf + o_fl, buf + o_ins, buf + o_st};
     (void)hipEventRecord(ss->in_ev[0], nullptr);
@@ -1812,17 +1881,14 @@ int kad_sr_insert(kad_searches* ss, uint32_t m, const uint32_t* which, const uin
     const hipError_t le = hipGetLastError();
     (void)hipEventRecord(ss->in_ev[1], nullptr);
     if (le != hipSuccess)
-        return done(set_error(KAD_ERR_HIP, (std::string("insert: launch failed: ") + hipGetErrorString(le)).c_str()));
+        return set_error(KAD_ERR_HIP, (std::string("insert: launch failed: ") + hipGetErrorString(le)).c_str());
     const hipError_t ce = hipMemcpy(h + o_ins, buf + o_ins, total - o_ins, hipMemcpyDeviceToHost);
     if (ce != hipSuccess)
-        return done(set_error(KAD_ERR_HIP, (std::string("insert: D2H failed: ") + hipGetErrorString(ce)).c_str()));
-    if (hipEventElapsedTime(&ss->in_ms, ss->in_ev[0], ss->in_ev[1]) != hipSuccess) {
-        (void)hipGetLastError();
-        ss->in_ms = 0.f;
-    }
+        return set_error(KAD_ERR_HIP, (std::string("insert: D2H failed: ") + hipGetErrorString(ce)).c_str());
+    ss->in_ms = elapsed_or_zero(ss->in_ev[0], ss->in_ev[1]);
     if (T) std::memcpy(out_inserted, h + o_ins, T);
     std::memcpy(out_status, h + o_st, m);
-    return done(KAD_OK);
+    return KAD_OK;
 }
 
 int kad_sr_insert_kernel_ms(const kad_searches* ss, float* out_ms) {
@@ -1884,11 +1950,9 @@ int kad_sr_try_insert_tick(kad_searches* ss, const uint8_t* cand_ids, const uint
     } catch (const std::bad_alloc&) {
         return set_error(KAD_ERR_NOMEM, "tick: out of host memory");
     }
-    DeviceGuard g(ss->device);
-    uint8_t* buf = nullptr;
+    CallScratch cs(ss->device);
     uint32_t n_rem = q, n_over = 0;
-    auto done = [&](int r) {
-        if (buf) (void)hipFree(buf);
+    auto done = [&](int r) {  // on every path: what was applied so far stands in the stats and the overflow count
         st.left = n_rem;
         st.overflowed = n_over;
         *out_n_overflow = n_over;
@@ -1896,15 +1960,9 @@ int kad_sr_try_insert_tick(kad_searches* ss, const uint8_t* cand_ids, const uint
         return r;
     };
     std::memset(out_kind, (int)KAD_SR_TICK_LEFT, q);
-    if (hipDeviceSynchronize() != hipSuccess)  // queries enqueued before the call read the old set
-        return done(set_error(KAD_ERR_HIP, "tick: device in error"));
-    if (hipMalloc((void**)&buf, total) != hipSuccess) {
-        (void)hipGetLastError();
-        buf = nullptr;
-        return done(set_error(KAD_ERR_NOMEM, "tick: out of device memory"));
-    }
-    for (hipEvent_t& e : ss->tk_ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) return done(set_error(KAD_ERR_HIP, "tick: no events"));
+    if (int rc = cs.open(total, "tick")) return done(rc);
+    uint8_t* const buf = cs.buf;
+    if (!have_events(ss->tk_ev)) return done(set_error(KAD_ERR_HIP, "tick: no events"));
     if (hipMemcpy(buf, cand_ids, 20ull * q, hipMemcpyHostToDevice) != hipSuccess ||
         (cand_flags ? hipMemcpy(buf + o_fl, cand_flags, q, hipMemcpyHostToDevice)
                     : hipMemset(buf + o_fl, 0, q)) != hipSuccess)
@@ -1934,11 +1992,7 @@ int kad_sr_try_insert_tick(kad_searches* ss, const uint8_t* cand_ids, const uint
         le = hipMemcpy(h_ver.data(), buf + o_ver, 16ull * r, hipMemcpyDeviceToHost);
         if (le != hipSuccess)
             return done(set_error(KAD_ERR_HIP, (std::string("tick: D2H of the verdicts failed: ") + hipGetErrorString(le)).c_str()));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ss->tk_ev[0], ss->tk_ev[1]) == hipSuccess)
-            st.verdict_ms += ms;
-        else
-            (void)hipGetLastError();
+        st.verdict_ms += elapsed_or_zero(ss->tk_ev[0], ss->tk_ev[1]);
         for (uint32_t k = 0; k < r; k++) {
             lb[k] = h_ver[4ull * k];
             fwd[k] = h_ver[4ull * k + 1];
@@ -1996,10 +2050,7 @@ int kad_sr_try_insert_tick(kad_searches* ss, const uint8_t* cand_ids, const uint
             le = hipMemcpy(h_res.data(), buf + o_ins, 2ull * m, hipMemcpyDeviceToHost);
             if (le != hipSuccess)
                 return done(set_error(KAD_ERR_HIP, (std::string("tick: D2H of the results failed: ") + hipGetErrorString(le)).c_str()));
-            if (hipEventElapsedTime(&ms, ss->tk_ev[2], ss->tk_ev[3]) == hipSuccess)
-                st.insert_ms += ms;
-            else
-                (void)hipGetLastError();
+            st.insert_ms += elapsed_or_zero(ss->tk_ev[2], ss->tk_ev[3]);
             st.pairs += m;
             for (uint32_t i = 0; i < m; i++) {
                 if (h_res[m + i] == KAD_SR_INSERT_OVERFLOW) {
@@ -2093,8 +2144,7 @@ int kad_sr_mark_nodes(kad_searches* ss, uint32_t q, const uint8_t* node_ids, con
         buf = nullptr;
         return done(set_error(KAD_ERR_NOMEM, "mark: out of device memory"));
     }
-    for (hipEvent_t& e : ss->mk_ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) return done(set_error(KAD_ERR_HIP, "mark: no events"));
+    if (!have_events(ss->mk_ev)) return done(set_error(KAD_ERR_HIP, "mark: no events"));
     // the scratch is laid out for mk_cap searches; only the part of the current S is used
     const size_t cap_bitmap = 4ull * (((size_t)ss->mk_cap + 31) / 32);
     // the count, the (search, count word) pairs of the last call, the bitmap, the list
@@ -2217,34 +2267,23 @@ int mark_entry_bits(kad_searches* ss, uint32_t p, const uint32_t* pair_which, co
     std::memcpy(h + o_pw, plan.pw.data(), 4ull * p);
     std::memcpy(h + o_clear, plan.pclear.data(), p);
     std::memcpy(h + o_set, plan.pset.data(), p);
-    DeviceGuard g(ss->device);
-    uint8_t* buf = nullptr;
-    auto done = [&](int r) {
-        if (buf) (void)hipFree(buf);
-        delete[] h;
-        return r;
-    };
-    if (hipDeviceSynchronize() != hipSuccess)  // queries enqueued before the call read the old set
-        return done(set_error(KAD_ERR_HIP, "mark entries: device in error"));
-    if (hipMalloc((void**)&buf, total) != hipSuccess) {
-        (void)hipGetLastError();
-        buf = nullptr;
-        return done(set_error(KAD_ERR_NOMEM, "mark entries: out of device memory"));
-    }
+    CallScratch cs(ss->device, h);
+    if (int rc = cs.open(total, "mark entries")) return rc;
+    uint8_t* const buf = cs.buf;
     if (hipMemcpy(buf, h, o_found, hipMemcpyHostToDevice) != hipSuccess)
-        return done(set_error(KAD_ERR_HIP, "mark entries: H2D failed"));
+        return set_error(KAD_ERR_HIP, "mark entries: H2D failed");
     const DevEntries D{ss->rec, ss->mkey, ss->mtail, ss->mflag, ss->cap, p, (const uint32_t*)(buf + o_pw),
                        (const uint64_t*)buf, (const uint32_t*)(buf + o_tail), buf + o_clear, buf + o_set, buf + o_found};
     hipLaunchKernelGGL(entries_kernel, dim3((p + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, D);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess)
-        return done(set_error(KAD_ERR_HIP, (std::string("mark entries: launch failed: ") + hipGetErrorString(le)).c_str()));
+        return set_error(KAD_ERR_HIP, (std::string("mark entries: launch failed: ") + hipGetErrorString(le)).c_str());
     const hipError_t ce = hipMemcpy(h + o_found, buf + o_found, p, hipMemcpyDeviceToHost);
     if (ce != hipSuccess)
-        return done(set_error(KAD_ERR_HIP, (std::string("mark entries: D2H failed: ") + hipGetErrorString(ce)).c_str()));
+        return set_error(KAD_ERR_HIP, (std::string("mark entries: D2H failed: ") + hipGetErrorString(ce)).c_str());
     if (out_found)
         for (uint32_t k = 0; k < p; k++) out_found[plan.pord[k]] = h[o_found + k];
-    return done(KAD_OK);
+    return KAD_OK;
 }
 }  // namespace
 
@@ -2262,152 +2301,14 @@ int kad_sr_mark_due(kad_searches* ss, uint32_t p, const uint32_t* pair_which, co
 
 int kad_sr_step(kad_searches* ss, uint32_t m, const uint32_t* which, const uint8_t* mode, kad_step_out* out,
                 kad_sr_step_stats* out_stats) {
-    if (!ss || !out) return set_error(KAD_ERR_INVALID, "NULL search set or output");
-    std::string err;
-    if (int rc = kadplan::sr_step_check(ss->S, m, which, mode, err)) return set_error(rc, err.c_str());
-    kad_sr_step_stats st = {};
-    if (m == 0) {
-        if (out_stats) *out_stats = st;
-        return KAD_OK;
-    }
-    if (ss->cap > REFILL_MAX_CAP) return set_error(KAD_ERR_UNSUPPORTED, "kad_sr_step handles slabs of up to 64 entries");
-    static_assert(sizeof(kad_step_out) == 16, "one 16-byte store per search");
-    bool any_apply = false;
-    for (uint32_t k = 0; mode && k < m && !any_apply; k++) any_apply = (mode[k] & KAD_STEP_APPLY) != 0;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    // the call's scratch, one allocation: the listed searches and the modes (one upload each, when given), the results
-    // (one copy back), the count of searches to expire and their list
-    const size_t o_mode = which ? 4ull * m : 0, o_out = up16(o_mode + (mode ? m : 0)), o_head = o_out + 16ull * m,
-                 o_list = o_head + 16, total = o_list + 4ull * m;
-    DeviceGuard g(ss->device);
-    uint8_t* buf = nullptr;
-    auto done = [&](int r) {
-        if (buf) (void)hipFree(buf);
-        return r;
-    };
-    if (hipDeviceSynchronize() != hipSuccess)  // queries enqueued before the call read the old set
-        return done(set_error(KAD_ERR_HIP, "step: device in error"));
-    if (hipMalloc((void**)&buf, total) != hipSuccess) {
-        (void)hipGetLastError();
-        buf = nullptr;
-        return done(set_error(KAD_ERR_NOMEM, "step: out of device memory"));
-    }
-    for (hipEvent_t& e : ss->sp_ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) return done(set_error(KAD_ERR_HIP, "step: no events"));
-    if ((which && hipMemcpy(buf, which, 4ull * m, hipMemcpyHostToDevice) != hipSuccess) ||
-        (mode && hipMemcpy(buf + o_mode, mode, m, hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemsetAsync(buf + o_head, 0, 16, nullptr) != hipSuccess)
-        return done(set_error(KAD_ERR_HIP, "step: H2D failed"));
-    const DevStep D{ss->rec, ss->mkey, ss->mtail, ss->mflag, ss->S, ss->cap, m,
-                    which ? (const uint32_t*)buf : nullptr, mode ? buf + o_mode : nullptr, (u32x4_t*)(buf + o_out),
-                    (uint32_t*)(buf + o_head), (uint32_t*)(buf + o_list)};
-    (void)hipEventRecord(ss->sp_ev[0], nullptr);
-    if (ss->cap % 16 == 0)
-        hipLaunchKernelGGL(step_kernel<true>, dim3((m + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, D);
-    else
-        hipLaunchKernelGGL(step_kernel<false>, dim3((m + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, D);
-    hipError_t le = hipGetLastError();
-    if (le == hipSuccess && any_apply) {  // the grid is sized without the count: the waves stride over what the head says
-        const uint32_t blocks = (m + REFILL_WAVES - 1) / REFILL_WAVES, grid = blocks < MARK_FIX_GRID ? blocks : MARK_FIX_GRID;
-        hipLaunchKernelGGL(step_expire_kernel, dim3(grid), dim3(BLOCK), 0, nullptr, D);
-        le = hipGetLastError();
-    }
-    (void)hipEventRecord(ss->sp_ev[1], nullptr);
-    if (le != hipSuccess)
-        return done(set_error(KAD_ERR_HIP, (std::string("step: launch failed: ") + hipGetErrorString(le)).c_str()));
-    const hipError_t ce = hipMemcpy(out, buf + o_out, 16ull * m, hipMemcpyDeviceToHost);
-    if (ce != hipSuccess)
-        return done(set_error(KAD_ERR_HIP, (std::string("step: D2H failed: ") + hipGetErrorString(ce)).c_str()));
-    if (hipEventElapsedTime(&st.kernel_ms, ss->sp_ev[0], ss->sp_ev[1]) != hipSuccess) {
-        (void)hipGetLastError();
-        st.kernel_ms = 0.f;
-    }
-    if (out_stats) {
-        for (uint32_t k = 0; k < m; k++) {
-            st.synced += (out[k].bits & KAD_STEP_SYNCED) ? 1u : 0u;
-            st.expired += (out[k].bits & KAD_STEP_EXPIRE) ? 1u : 0u;
-            st.skipped += (out[k].bits & KAD_STEP_SKIPPED) ? 1u : 0u;
-            st.picks += (uint32_t)__builtin_popcountll(out[k].picks);
-        }
-        *out_stats = st;
-    }
-    return done(KAD_OK);
+    return step_call(ss, m, which, mode, out, out_stats, kadplan::sr_step_check, "step",
+                     "kad_sr_step handles slabs of up to 64 entries");
 }
 
 int kad_sr_step_full(kad_searches* ss, uint32_t m, const uint32_t* which, const uint8_t* mode, kad_step_full_out* out,
                      kad_sr_step_full_stats* out_stats) {
-    if (!ss || !out) return set_error(KAD_ERR_INVALID, "NULL search set or output");
-    std::string err;
-    if (int rc = kadplan::sr_step_full_check(ss->S, m, which, mode, err)) return set_error(rc, err.c_str());
-    kad_sr_step_full_stats st = {};
-    if (m == 0) {
-        if (out_stats) *out_stats = st;
-        return KAD_OK;
-    }
-    if (ss->cap > REFILL_MAX_CAP)
-        return set_error(KAD_ERR_UNSUPPORTED, "kad_sr_step_full handles slabs of up to 64 entries");
-    static_assert(sizeof(kad_step_full_out) == 32, "two 16-byte stores per search");
-    bool any_apply = false;
-    for (uint32_t k = 0; mode && k < m && !any_apply; k++) any_apply = (mode[k] & KAD_STEP_APPLY) != 0;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    // the call's scratch, one allocation, laid out as kad_sr_step's with 32 bytes of result per search
-    const size_t o_mode = which ? 4ull * m : 0, o_out = up16(o_mode + (mode ? m : 0)), o_head = o_out + 32ull * m,
-                 o_list = o_head + 16, total = o_list + 4ull * m;
-    DeviceGuard g(ss->device);
-    uint8_t* buf = nullptr;
-    auto done = [&](int r) {
-        if (buf) (void)hipFree(buf);
-        return r;
-    };
-    if (hipDeviceSynchronize() != hipSuccess)  // queries enqueued before the call read the old set
-        return done(set_error(KAD_ERR_HIP, "step full: device in error"));
-    if (hipMalloc((void**)&buf, total) != hipSuccess) {
-        (void)hipGetLastError();
-        buf = nullptr;
-        return done(set_error(KAD_ERR_NOMEM, "step full: out of device memory"));
-    }
-    for (hipEvent_t& e : ss->sp_ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) return done(set_error(KAD_ERR_HIP, "step full: no events"));
-    if ((which && hipMemcpy(buf, which, 4ull * m, hipMemcpyHostToDevice) != hipSuccess) ||
-        (mode && hipMemcpy(buf + o_mode, mode, m, hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemsetAsync(buf + o_head, 0, 16, nullptr) != hipSuccess)
-        return done(set_error(KAD_ERR_HIP, "step full: H2D failed"));
-    const DevStep D{ss->rec, ss->mkey, ss->mtail, ss->mflag, ss->S, ss->cap, m,
-                    which ? (const uint32_t*)buf : nullptr, mode ? buf + o_mode : nullptr, (u32x4_t*)(buf + o_out),
-                    (uint32_t*)(buf + o_head), (uint32_t*)(buf + o_list)};
-    (void)hipEventRecord(ss->sp_ev[0], nullptr);
-    if (ss->cap % 16 == 0)
-        hipLaunchKernelGGL(step_full_kernel<true>, dim3((m + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, D);
-    else
-        hipLaunchKernelGGL(step_full_kernel<false>, dim3((m + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, nullptr, D);
-    hipError_t le = hipGetLastError();
-    if (le == hipSuccess && any_apply) {  // the grid is sized without the count: the waves stride over what the head says
-        const uint32_t blocks = (m + REFILL_WAVES - 1) / REFILL_WAVES, grid = blocks < MARK_FIX_GRID ? blocks : MARK_FIX_GRID;
-        hipLaunchKernelGGL(step_expire_kernel, dim3(grid), dim3(BLOCK), 0, nullptr, D);
-        le = hipGetLastError();
-    }
-    (void)hipEventRecord(ss->sp_ev[1], nullptr);
-    if (le != hipSuccess)
-        return done(set_error(KAD_ERR_HIP, (std::string("step full: launch failed: ") + hipGetErrorString(le)).c_str()));
-    const hipError_t ce = hipMemcpy(out, buf + o_out, 32ull * m, hipMemcpyDeviceToHost);
-    if (ce != hipSuccess)
-        return done(set_error(KAD_ERR_HIP, (std::string("step full: D2H failed: ") + hipGetErrorString(ce)).c_str()));
-    if (hipEventElapsedTime(&st.kernel_ms, ss->sp_ev[0], ss->sp_ev[1]) != hipSuccess) {
-        (void)hipGetLastError();
-        st.kernel_ms = 0.f;
-    }
-    if (out_stats) {
-        for (uint32_t k = 0; k < m; k++) {
-            st.synced += (out[k].bits & KAD_STEP_SYNCED) ? 1u : 0u;
-            st.expired += (out[k].bits & KAD_STEP_EXPIRE) ? 1u : 0u;
-            st.skipped += (out[k].bits & KAD_STEP_SKIPPED) ? 1u : 0u;
-            st.picks += (uint32_t)__builtin_popcountll(out[k].picks);
-            st.listens += (uint32_t)__builtin_popcountll(out[k].listen);
-            st.announces += (uint32_t)__builtin_popcountll(out[k].announce);
-        }
-        *out_stats = st;
-    }
-    return done(KAD_OK);
+    return step_call(ss, m, which, mode, out, out_stats, kadplan::sr_step_full_check, "step full",
+                     "kad_sr_step_full handles slabs of up to 64 entries");
 }
 
 int kad_sr_try_insert_batch_host(const kad_searches* ss, const uint8_t* ids, uint32_t q, uint32_t* out_lb,

@@ -406,15 +406,39 @@ int sr_step_full_check(uint32_t S, uint32_t m, const uint32_t* which, const uint
 
 }  // namespace kadplan
 
+namespace {
+// the flag bytes of a list of n <= 64 entries four at a time, as the kernel's words hold them: entry 4i + b is byte b
+// of w[i], zero from n on
+void flag_words(uint32_t n, const uint8_t* node_flags, uint32_t (&w)[16]) {
+    for (uint32_t i = 0; i < 16; i++) w[i] = 0;
+    for (uint32_t e = 0; e < n; e++) w[e / 4u] |= (uint32_t)node_flags[e] << (8u * (e % 4u));
+}
+
+bool step_mode_ok(uint32_t mode) { return !(mode & ~kadstep::MODE_BITS); }
+
+// kad_search_step_batch and kad_search_step_full_batch: `step` on every list of the CSR, after every list and mode passed
+template <class Out>
+int step_lists(uint32_t m, const uint32_t* off, const uint8_t* node_flags, const uint8_t* search_flags, const uint8_t* mode,
+               Out* out, bool (*mode_ok)(uint32_t), int (*step)(uint32_t, const uint8_t*, uint32_t, uint32_t, Out*)) {
+    if (m == 0) return KAD_OK;
+    if (!off || !out || (off[m] && !node_flags)) return KAD_ERR_INVALID;
+    for (uint32_t k = 0; k < m; k++)
+        if (off[k + 1] < off[k] || off[k + 1] - off[k] > 64u || (mode && !mode_ok(mode[k]))) return KAD_ERR_INVALID;
+    for (uint32_t k = 0; k < m; k++)
+        if (int rc = step(off[k + 1] - off[k], node_flags + off[k], search_flags ? search_flags[k] : 0u, mode ? mode[k] : 0u,
+                          out + k))
+            return rc;
+    return KAD_OK;
+}
+}  // namespace
+
 extern "C" int kad_search_step_full(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t mode,
                                     kad_step_full_out* out) {
     if ((n && !node_flags) || !out || n > 64u || !kadstep::full_mode_ok(mode)) return KAD_ERR_INVALID;
+    uint32_t w[16];
+    flag_words(n, node_flags, w);
     kadstep::PlanesFull P;
-    for (uint32_t i = 0; 4u * i < n; i++) {  // the flag bytes four at a time, as the kernel's words hold them
-        uint32_t w = 0;
-        for (uint32_t b = 0; b < 4u && 4u * i + b < n; b++) w |= (uint32_t)node_flags[4u * i + b] << (8u * b);
-        kadstep::add_word_full(P, w, i);
-    }
+    for (uint32_t i = 0; i < 16; i++) kadstep::add_word_full(P, w[i], i);
     const kadstep::DecisionFull d = kadstep::decide_full(P, n, (search_flags & KAD_SR_EXPIRED) != 0, mode);
     out->picks = d.picks;
     out->listen = d.listen;
@@ -426,27 +450,16 @@ extern "C" int kad_search_step_full(uint32_t n, const uint8_t* node_flags, uint3
 
 extern "C" int kad_search_step_full_batch(uint32_t m, const uint32_t* off, const uint8_t* node_flags,
                                           const uint8_t* search_flags, const uint8_t* mode, kad_step_full_out* out) {
-    if (m == 0) return KAD_OK;
-    if (!off || !out || (off[m] && !node_flags)) return KAD_ERR_INVALID;
-    for (uint32_t k = 0; k < m; k++)
-        if (off[k + 1] < off[k] || off[k + 1] - off[k] > 64u || (mode && !kadstep::full_mode_ok(mode[k])))
-            return KAD_ERR_INVALID;
-    for (uint32_t k = 0; k < m; k++)
-        if (int rc = kad_search_step_full(off[k + 1] - off[k], node_flags + off[k], search_flags ? search_flags[k] : 0u,
-                                          mode ? mode[k] : 0u, out + k))
-            return rc;
-    return KAD_OK;
+    return step_lists(m, off, node_flags, search_flags, mode, out, kadstep::full_mode_ok, kad_search_step_full);
 }
 
 extern "C" int kad_search_step(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t mode,
                                kad_step_out* out) {
-    if ((n && !node_flags) || !out || n > 64u || (mode & ~kadstep::MODE_BITS)) return KAD_ERR_INVALID;
+    if ((n && !node_flags) || !out || n > 64u || !step_mode_ok(mode)) return KAD_ERR_INVALID;
+    uint32_t w[16];
+    flag_words(n, node_flags, w);
     kadstep::Planes P;
-    for (uint32_t i = 0; 4u * i < n; i++) {  // the flag bytes four at a time, as the kernel's words hold them
-        uint32_t w = 0;
-        for (uint32_t b = 0; b < 4u && 4u * i + b < n; b++) w |= (uint32_t)node_flags[4u * i + b] << (8u * b);
-        kadstep::add_word(P, w, i);
-    }
+    for (uint32_t i = 0; i < 16; i++) kadstep::add_word(P, w[i], i);
     const kadstep::Decision d = kadstep::decide(P, n, (search_flags & KAD_SR_EXPIRED) != 0, mode);
     out->picks = d.picks;
     out->counts = d.counts;
@@ -456,16 +469,7 @@ extern "C" int kad_search_step(uint32_t n, const uint8_t* node_flags, uint32_t s
 
 extern "C" int kad_search_step_batch(uint32_t m, const uint32_t* off, const uint8_t* node_flags,
                                      const uint8_t* search_flags, const uint8_t* mode, kad_step_out* out) {
-    if (m == 0) return KAD_OK;
-    if (!off || !out || (off[m] && !node_flags)) return KAD_ERR_INVALID;
-    for (uint32_t k = 0; k < m; k++)
-        if (off[k + 1] < off[k] || off[k + 1] - off[k] > 64u || (mode && (mode[k] & ~kadstep::MODE_BITS)))
-            return KAD_ERR_INVALID;
-    for (uint32_t k = 0; k < m; k++)
-        if (int rc = kad_search_step(off[k + 1] - off[k], node_flags + off[k], search_flags ? search_flags[k] : 0u,
-                                     mode ? mode[k] : 0u, out + k))
-            return rc;
-    return KAD_OK;
+    return step_lists(m, off, node_flags, search_flags, mode, out, step_mode_ok, kad_search_step);
 }
 
 extern "C" int kad_search_trim(uint32_t n, const uint8_t* node_flags, uint32_t search_flags, uint32_t* full,

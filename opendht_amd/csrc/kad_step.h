@@ -1,9 +1,10 @@
 // Dht::searchStep's decision on one search's list (dht.cpp:1344-1464), DESIGN.md §7.19: written once, over bit planes
-// of the member flag bytes, for the host (kad_search_step) and for step_kernel of kad_searches.hip, which call the same
-// functions. Plain C++ without a loop over the entries: popcounts, trailing-zero counts and a fixed number of
-// lowest-bit removals. No HIP call and no header beyond <cstdint>, so the CPU sanitizer build compiles it alone.
+// of the member flag bytes, for the host (kad_search_step) and for step_lane of kad_searches.hip (the body of step_kernel
+// and step_full_kernel), which call the same functions. Plain C++ without a loop over the entries: popcounts,
+// trailing-zero counts and a fixed number of lowest-bit removals. No HIP call and no header beyond <cstdint>, so the CPU
+// sanitizer build compiles it alone.
 // decide_full adds the listen loop and the announce probes of a synced search over two more planes and
-// hands the get loop to decide; kad_search_step_full and step_full_kernel call it.
+// hands the get loop to decide; kad_search_step_full and step_lane<WIDE, true> call it.
 #pragma once
 
 #include <cstdint>
@@ -51,11 +52,6 @@ KAD_STEP_HD void add_word(Planes& P, uint32_t w, uint32_t i) {
     P.pend |= gather4(w, 3) << sh;
     P.sync |= gather4(w, 4) << sh;
     P.noget |= gather4(w, 5) << sh;
-}
-
-// the byte mask that gives entries 4i .. 4i+3 of a flag word PENDING | NOGET where they are picked
-KAD_STEP_HD uint32_t sent_bytes(uint64_t picks, uint32_t i) {
-    return spread4((uint32_t)(picks >> (4u * i))) * (uint32_t)(KAD_SN_PENDING | KAD_SN_NOGET);
 }
 
 KAD_STEP_HD uint32_t pop64(uint64_t v) { return (uint32_t)__builtin_popcountll(v); }

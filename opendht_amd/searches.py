@@ -293,6 +293,10 @@ class DeviceSearches:
         request), n, bad, lead_bad, solicited (m,) uint8, bits (m,) uint32 of KAD_STEP_SKIPPED .. KAD_STEP_EXPIRE, and
         stats (kad_sr_step_stats as a dict). With KAD_STEP_APPLY the sends and expiries are written to the set.
         Synchronous."""
+        return self._step("kad_sr_step", STEP_OUT_DTYPE, sr_step_stats, which, modes)
+
+    def _which_modes(self, which, modes):
+        """step's arguments as the call takes them: which (m,) uint32 or None, m, modes (m,) uint8 or None."""
         if which is not None:
             which = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
         m = self.S if which is None else which.shape[0]
@@ -301,9 +305,13 @@ class DeviceSearches:
                      else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1))
             if modes.shape[0] != m:
                 raise ValueError("modes must have one byte per stepped search")
-        out, st = np.zeros(m, STEP_OUT_DTYPE), sr_step_stats()
-        check(lib().kad_sr_step(self._h, m, ptr(which), ptr(modes), ptr(out), C.byref(st)), "kad_sr_step")
-        return _step_fields(out, {n: getattr(st, n) for n, _ in sr_step_stats._fields_})
+        return which, m, modes
+
+    def _step(self, call, dtype, stats_cls, which, modes) -> dict:
+        which, m, modes = self._which_modes(which, modes)
+        out, st = np.zeros(m, dtype), stats_cls()
+        check(getattr(lib(), call)(self._h, m, ptr(which), ptr(modes), ptr(out), C.byref(st)), call)
+        return _step_fields(out, {n: getattr(st, n) for n, _ in stats_cls._fields_})
 
     def mark_due(self, which, ids, clear_bits=None, set_bits=None):
         """mark_entries for the two due bits (kad_sr_mark_due): clear_bits and set_bits over KAD_SN_LISTEN_DUE |
@@ -329,17 +337,7 @@ class DeviceSearches:
         KAD_STEP_ANNOUNCE and KAD_STEP_PROBE_BLOCKS. Returns step's arrays plus listen and announce (m,) uint64 (bit e:
         entry e gets the listen requests due on it / the announce probe); stats is kad_sr_step_full_stats as a dict.
         With KAD_STEP_APPLY the three kinds of sends and the expiries are written to the set. Synchronous."""
-        if which is not None:
-            which = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
-        m = self.S if which is None else which.shape[0]
-        if modes is not None:
-            modes = (np.full(m, modes, np.uint8) if np.isscalar(modes)
-                     else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1))
-            if modes.shape[0] != m:
-                raise ValueError("modes must have one byte per stepped search")
-        out, st = np.zeros(m, STEP_FULL_OUT_DTYPE), sr_step_full_stats()
-        check(lib().kad_sr_step_full(self._h, m, ptr(which), ptr(modes), ptr(out), C.byref(st)), "kad_sr_step_full")
-        return _step_fields(out, {n: getattr(st, n) for n, _ in sr_step_full_stats._fields_})
+        return self._step("kad_sr_step_full", STEP_FULL_OUT_DTYPE, sr_step_full_stats, which, modes)
 
     @property
     def refill_kernel_ms(self) -> float:
@@ -781,17 +779,19 @@ def _step_fields(out, stats=None) -> dict:
 def search_step(node_flags, search_flags: int = 0, mode: int = 0) -> dict:
     """Dht::searchStep's decision on one list from its flag bytes, on the host without a device (kad_search_step):
     picks (int mask of list positions), n, bad, lead_bad, solicited and bits (ints)."""
+    return _host_step("kad_search_step", STEP_OUT_DTYPE, "an unknown mode bit", node_flags, search_flags, mode)
+
+
+def _host_step(call, dtype, bad_mode, node_flags, search_flags, mode) -> dict:
     fl = np.ascontiguousarray(node_flags, dtype=np.uint8).reshape(-1)
-    out = np.zeros(1, STEP_OUT_DTYPE)
-    rc = lib().kad_search_step(fl.shape[0], ptr(fl) if fl.shape[0] else None, search_flags, mode, ptr(out))
+    out = np.zeros(1, dtype)
+    rc = getattr(lib(), call)(fl.shape[0], ptr(fl) if fl.shape[0] else None, search_flags, mode, ptr(out))
     if rc != 0:
-        raise ValueError(f"kad_search_step: {rc}: more than 64 entries or an unknown mode bit")
+        raise ValueError(f"{call}: {rc}: more than 64 entries or {bad_mode}")
     return {k: int(v[0]) for k, v in _step_fields(out).items()}
 
 
-def search_step_batch(off, node_flags, search_flags=None, modes=None) -> dict:
-    """search_step on m lists in CSR form (off (m + 1,) uint32 into node_flags; search_flags and modes (m,) uint8 or
-    None), on the host (kad_search_step_batch): the arrays DeviceSearches.step returns, without stats."""
+def _host_step_batch(call, dtype, bad_mode, off, node_flags, search_flags, modes) -> dict:
     off = np.ascontiguousarray(off, dtype=np.uint32).reshape(-1)
     m = off.shape[0] - 1
     fl = np.ascontiguousarray(node_flags, dtype=np.uint8).reshape(-1)
@@ -799,11 +799,18 @@ def search_step_batch(off, node_flags, search_flags=None, modes=None) -> dict:
     md = None if modes is None else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1)
     if m < 0 or fl.shape[0] < int(off[-1]) or any(a is not None and a.shape[0] != m for a in (sf, md)):
         raise ValueError("off needs m + 1 offsets into node_flags, search_flags and modes one byte per list")
-    out = np.zeros(m, STEP_OUT_DTYPE)
-    rc = lib().kad_search_step_batch(m, ptr(off), ptr(fl) if fl.shape[0] else None, ptr(sf), ptr(md), ptr(out))
+    out = np.zeros(m, dtype)
+    rc = getattr(lib(), call)(m, ptr(off), ptr(fl) if fl.shape[0] else None, ptr(sf), ptr(md), ptr(out))
     if rc != 0:
-        raise ValueError(f"kad_search_step_batch: {rc}: offsets descending, a list of more than 64 entries or an unknown mode bit")
+        raise ValueError(f"{call}: {rc}: offsets descending, a list of more than 64 entries or {bad_mode}")
     return _step_fields(out)
+
+
+def search_step_batch(off, node_flags, search_flags=None, modes=None) -> dict:
+    """search_step on m lists in CSR form (off (m + 1,) uint32 into node_flags; search_flags and modes (m,) uint8 or
+    None), on the host (kad_search_step_batch): the arrays DeviceSearches.step returns, without stats."""
+    return _host_step_batch("kad_search_step_batch", STEP_OUT_DTYPE, "an unknown mode bit", off, node_flags, search_flags,
+                            modes)
 
 
 def step_searches(DS, host, which, modes, now) -> dict:
@@ -818,32 +825,47 @@ def step_searches(DS, host, which, modes, now) -> dict:
 
     Returns {"synced", "short", "done", "exhausted", "expire", "skipped"} (lists of searches), "picks" ({search: list
     positions}) and "stats"."""
+    return _step_and_replay("step_searches", DS, DS.step, ("picks",), host, which, modes, now)
+
+
+def _positions(mask) -> list:
+    return [e for e in range(64) if (int(mask) >> e) & 1]
+
+
+def _step_and_replay(name, DS, step, sends, host, which, modes, now) -> dict:
+    """step_searches (sends = ("picks",)) and step_searches_full (("picks", "listen", "announce")): host.step's tuple and
+    the device's answer both open with one list of positions per name in `sends`, then n, bad, lead_bad, solicited, bits."""
     idx = np.arange(DS.S, dtype=np.uint32) if which is None else np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
     m = idx.shape[0]
     md = np.zeros(m, np.uint8) if modes is None else (np.full(m, modes, np.uint8) if np.isscalar(modes)
                                                       else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1))
     want = [host.step(int(s), int(md[k]), now) for k, s in enumerate(idx)]
-    r = DS.step(which, md)
-    out = {"synced": [], "short": [], "done": [], "exhausted": [], "expire": [], "skipped": [], "picks": {},
-           "stats": r["stats"]}
+    r = step(which, md)
+    out = {"synced": [], "short": [], "done": [], "exhausted": [], "expire": [], "skipped": []}
+    out.update({f: {} for f in sends}, stats=r["stats"])
     names = ((KAD_STEP_SYNCED, "synced"), (KAD_STEP_SHORT, "short"), (KAD_STEP_DONE, "done"),
              (KAD_STEP_EXHAUSTED, "exhausted"), (KAD_STEP_EXPIRE, "expire"), (KAD_STEP_SKIPPED, "skipped"))
     for k, s in enumerate(idx):
-        picks = [e for e in range(64) if (int(r["picks"][k]) >> e) & 1]
-        got = (picks, int(r["n"][k]), int(r["bad"][k]), int(r["lead_bad"][k]), int(r["solicited"][k]), int(r["bits"][k]))
+        got = tuple(_positions(r[f][k]) for f in sends) + tuple(
+            int(r[f][k]) for f in ("n", "bad", "lead_bad", "solicited", "bits"))
         w = want[k]
-        if got != (list(w[0]),) + tuple(int(v) for v in w[1:]):
-            raise RuntimeError(f"step_searches: search {int(s)} stepped to {w} on the host, {got} on the device")
+        if got != tuple(list(v) for v in w[:len(sends)]) + tuple(int(v) for v in w[len(sends):]):
+            raise RuntimeError(f"{name}: search {int(s)} stepped to {w} on the host, {got} on the device")
     for k, s in enumerate(idx):
         s, bits = int(s), int(r["bits"][k])
-        picks = want[k][0]
-        if picks:
-            out["picks"][s] = list(picks)
-        for bit, name in names:
+        pos = dict(zip(sends, want[k]))
+        for f in sends:
+            if pos[f]:
+                out[f][s] = list(pos[f])
+        for bit, flag in names:
             if bits & bit:
-                out[name].append(s)
-        if md[k] & KAD_STEP_APPLY:
-            for e in picks:
+                out[flag].append(s)
+        if md[k] & KAD_STEP_APPLY:  # the reference's order: listens, probes, gets, then the expiry
+            for e in pos.get("listen", ()):
+                host.listen(s, e, now)
+            for e in pos.get("announce", ()):
+                host.announce_probe(s, e, now, bool(md[k] & KAD_STEP_PROBE_BLOCKS))
+            for e in pos["picks"]:
                 host.send(s, e, now)
             if bits & KAD_STEP_EXPIRE and not md[k] & KAD_STEP_NO_EXPIRE:
                 host.expire(s)
@@ -852,29 +874,14 @@ def step_searches(DS, host, which, modes, now) -> dict:
 
 def search_step_full(node_flags, search_flags: int = 0, mode: int = 0) -> dict:
     """search_step with the listen and announce sends (kad_search_step_full): also listen and announce (int masks)."""
-    fl = np.ascontiguousarray(node_flags, dtype=np.uint8).reshape(-1)
-    out = np.zeros(1, STEP_FULL_OUT_DTYPE)
-    rc = lib().kad_search_step_full(fl.shape[0], ptr(fl) if fl.shape[0] else None, search_flags, mode, ptr(out))
-    if rc != 0:
-        raise ValueError(f"kad_search_step_full: {rc}: more than 64 entries or an invalid mode")
-    return {k: int(v[0]) for k, v in _step_fields(out).items()}
+    return _host_step("kad_search_step_full", STEP_FULL_OUT_DTYPE, "an invalid mode", node_flags, search_flags, mode)
 
 
 def search_step_full_batch(off, node_flags, search_flags=None, modes=None) -> dict:
     """search_step_full on m lists in CSR form, as search_step_batch (kad_search_step_full_batch): the arrays
     DeviceSearches.step_full returns, without stats."""
-    off = np.ascontiguousarray(off, dtype=np.uint32).reshape(-1)
-    m = off.shape[0] - 1
-    fl = np.ascontiguousarray(node_flags, dtype=np.uint8).reshape(-1)
-    sf = None if search_flags is None else np.ascontiguousarray(search_flags, dtype=np.uint8).reshape(-1)
-    md = None if modes is None else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1)
-    if m < 0 or fl.shape[0] < int(off[-1]) or any(a is not None and a.shape[0] != m for a in (sf, md)):
-        raise ValueError("off needs m + 1 offsets into node_flags, search_flags and modes one byte per list")
-    out = np.zeros(m, STEP_FULL_OUT_DTYPE)
-    rc = lib().kad_search_step_full_batch(m, ptr(off), ptr(fl) if fl.shape[0] else None, ptr(sf), ptr(md), ptr(out))
-    if rc != 0:
-        raise ValueError(f"kad_search_step_full_batch: {rc}: offsets descending, a list of more than 64 entries or an invalid mode")
-    return _step_fields(out)
+    return _host_step_batch("kad_search_step_full_batch", STEP_FULL_OUT_DTYPE, "an invalid mode", off, node_flags,
+                            search_flags, modes)
 
 
 def _positions(mask) -> list:
@@ -893,40 +900,8 @@ def step_searches_full(DS, host, which, modes, now) -> dict:
     unless the mode has KAD_STEP_NO_EXPIRE.
 
     Returns step_searches' dict plus "listen" and "announce" ({search: list positions})."""
-    idx = np.arange(DS.S, dtype=np.uint32) if which is None else np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
-    m = idx.shape[0]
-    md = np.zeros(m, np.uint8) if modes is None else (np.full(m, modes, np.uint8) if np.isscalar(modes)
-                                                      else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1))
-    want = [host.step(int(s), int(md[k]), now) for k, s in enumerate(idx)]
-    r = DS.step_full(which, md)
-    out = {"synced": [], "short": [], "done": [], "exhausted": [], "expire": [], "skipped": [], "picks": {},
-           "listen": {}, "announce": {}, "stats": r["stats"]}
-    names = ((KAD_STEP_SYNCED, "synced"), (KAD_STEP_SHORT, "short"), (KAD_STEP_DONE, "done"),
-             (KAD_STEP_EXHAUSTED, "exhausted"), (KAD_STEP_EXPIRE, "expire"), (KAD_STEP_SKIPPED, "skipped"))
-    for k, s in enumerate(idx):
-        got = (_positions(r["picks"][k]), _positions(r["listen"][k]), _positions(r["announce"][k]), int(r["n"][k]),
-               int(r["bad"][k]), int(r["lead_bad"][k]), int(r["solicited"][k]), int(r["bits"][k]))
-        w = want[k]
-        if got != tuple(list(v) for v in w[:3]) + tuple(int(v) for v in w[3:]):
-            raise RuntimeError(f"step_searches_full: search {int(s)} stepped to {w} on the host, {got} on the device")
-    for k, s in enumerate(idx):
-        s, bits = int(s), int(r["bits"][k])
-        for name, pos in zip(("picks", "listen", "announce"), want[k][:3]):
-            if pos:
-                out[name][s] = list(pos)
-        for bit, name in names:
-            if bits & bit:
-                out[name].append(s)
-        if md[k] & KAD_STEP_APPLY:
-            for e in want[k][1]:
-                host.listen(s, e, now)
-            for e in want[k][2]:
-                host.announce_probe(s, e, now, bool(md[k] & KAD_STEP_PROBE_BLOCKS))
-            for e in want[k][0]:
-                host.send(s, e, now)
-            if bits & KAD_STEP_EXPIRE and not md[k] & KAD_STEP_NO_EXPIRE:
-                host.expire(s)
-    return out
+    return _step_and_replay("step_searches_full", DS, DS.step_full, ("picks", "listen", "announce"), host, which, modes,
+                            now)
 
 
 def refill_searches(DS: DeviceSearches, NC, host, which, now) -> dict:
