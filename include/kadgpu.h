@@ -1181,10 +1181,14 @@ int kad_shard_run(kad_comm* comm, const kad_table* shard, const uint32_t* global
  * (KAD_ADDR4_LEN or KAD_ADDR6_LEN). Synchronous. */
 int kad_table_set_addrs(kad_table* t, uint32_t addr_len, const uint8_t* addrs);
 /* Batched NetworkEngine::bufferNodes(af, id, nodes) (network_engine.cpp:942-974): for query i the
- * candidates idx[i*k .. i*k + cnt[i]) (node indices incl. index_base, e.g. a findClosestNodes or
- * getCachedNodes result; cnt may be NULL: entries up to the first KAD_NO_NODE), sorted by XOR
- * distance to targets[i], the first KAD_SEND_NODES packed as ID + address records into
- * out[i * KAD_SEND_NODES * (20 + addr_len)]; out_n[i] = records written. Device pointers. */
+ * candidates idx[i*k .. i*k + min(cnt[i], k)) (node indices incl. index_base, e.g. a findClosestNodes or
+ * getCachedNodes result; cnt[i] > k is clamped to k; cnt may be NULL: all k entries of the row). An entry
+ * equal to KAD_NO_NODE, or outside [index_base, index_base + n_nodes), is skipped wherever it stands, and
+ * the entries after it still count. The others are sorted by XOR distance to targets[i] (equal distances,
+ * i.e. equal IDs, keep their order in the row) and the first KAD_SEND_NODES are packed as ID + address
+ * records into out[i * KAD_SEND_NODES * (20 + addr_len)], the rest of the row zeroed; out_n[i] (may be
+ * NULL) = records written. out must be 16-byte aligned, k <= KAD_MAX_COUNT; idx may be NULL when k is 0.
+ * Device pointers. */
 int kad_buffer_nodes_batch(const kad_table* t, const uint8_t* targets, uint32_t q, const uint32_t* idx,
                            const uint8_t* cnt, uint32_t k, uint8_t* out, uint8_t* out_n, void* stream);
 /* NetworkEngine::deserializeNodes' filter (network_engine.cpp:788-828): for n records of rec_len

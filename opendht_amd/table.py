@@ -303,8 +303,10 @@ class DeviceTable:
 
     def buffer_nodes(self, targets, idx, cnt=None, stream=None):
         """NetworkEngine::bufferNodes per query (network_engine.cpp:942-974) over device tensors: the
-        candidates of row i of idx (cnt[i] of them, or up to the first KAD_NO_NODE) sorted by XOR
-        distance, the first 8 packed as 26- / 38-byte records. Returns (out (q, 8 * rec) uint8, n (q,))."""
+        candidates of row i of idx (the first min(cnt[i], k) entries, or all k without cnt) sorted by XOR
+        distance, the first 8 packed as 26- / 38-byte records. Entries equal to KAD_NO_NODE or outside
+        [index_base, index_base + n) are skipped wherever they stand, and what follows them still counts;
+        equal distances keep row order. Returns (out (q, 8 * rec) uint8, zero beyond the records, n (q,))."""
         import torch
 
         q, k = idx.shape
