@@ -264,7 +264,7 @@ int kad_table_export_lines(const kad_table* t, uint32_t set, void* out, uint64_t
  * `cap`; totals always carries the true counts, so an overflow shows as totals.expired > cap_nodes.
  * Any table shape: split-policy, uniform and shard tables, buckets of any width, empty buckets, n_buckets == 0
  * (NodeCache-only: the node counts, no buckets), n_nodes == 0. getNodesStats' `cached` (Bucket::cached, a host
- * pointer per bucket) and bucketMaintenance's Bucket::time stay with the host.
+ * pointer per bucket) stays with the host; bucketMaintenance's Bucket::time has its own pass, kad_table_maintenance.
  * Device pointers (4-byte aligned); enqueues on `stream` and does not synchronise. A const query whose partial
  * counts live in a stream-ordered allocation of the call's own: concurrent sweeps of one table on distinct streams
  * are safe. Checked in this order, before any device work: NULL table, NULL totals, unknown flag bits, a NULL list
@@ -305,6 +305,89 @@ int kad_table_sweep_host(const kad_table* t, uint32_t flags, kad_sweep_totals* t
  * what it is given back, up to 32 MB after a kad_table_expire that took more (the rest is returned to the driver). */
 int kad_table_expire(kad_table* t, uint32_t* remap, uint32_t* removed, uint32_t cap_removed, uint32_t* n_removed,
                      uint32_t* changed_buckets, uint32_t cap_buckets, uint32_t* n_changed);
+
+/* ---- bucket times and Dht::bucketMaintenance's scan (dht.cpp:2826-2885, 3174-3181) ---- */
+/* Bucket::time (routing_table.h:30,34) on the device: one int64 per bucket, nanoseconds of steady_clock, INT64_MIN for
+ * time_point::min() (Bucket's default, and what connectivityChanged resets to, dht.cpp:2391). The array is allocated
+ * on first use; a table that never had bucket times set behaves as if every bucket were at INT64_MIN.
+ * kad_table_apply carries the times: REMOVE, REPLACE and INSERT leave them, KAD_OP_SPLIT a gives the new bucket a + 1
+ * the time of bucket a (routing_table.cpp:149); kad_table_expire keeps them. None of these calls ends the resident
+ * query service (no query reads the times). A failure leaves the table unchanged.
+ * Upload every bucket's time: host array of n_buckets entries; NULL sets every bucket to INT64_MIN. Synchronous. */
+int kad_table_set_bucket_times(kad_table* t, const int64_t* time_ns);
+/* buckets[j] gets time_ns[j] (host lists of m entries), for a caller that already knows the bucket. A bucket listed
+ * twice takes the later entry. Checked before any device work: NULL table, a NULL list with m > 0, an index
+ * >= n_buckets (all KAD_ERR_INVALID; nothing is written). Synchronous. */
+int kad_table_patch_bucket_times(kad_table* t, uint32_t m, const uint32_t* buckets, const int64_t* time_ns);
+/* The times as a host array of n_buckets entries, ordered after every change made before the call. */
+int kad_table_get_bucket_times(const kad_table* t, int64_t* out);
+/* Dht::onReportedAddr (dht.cpp:3174-3181) x q: findBucket(ids[i])->time = now_ns for every ID (device, q x 20
+ * bytes). out_bucket (device, q words, may be NULL) receives the bucket, as kad_rt_find_bucket_batch gives it. A call
+ * has one now_ns, so IDs that share a bucket store the same value: the result does not depend on the order lanes run.
+ * Enqueues on `stream` and does not synchronise. Checked in this order: NULL table, n_buckets == 0 (the reference
+ * dereferences end()), a NULL ids with q > 0 (all KAD_ERR_INVALID). */
+int kad_table_touch_buckets(kad_table* t, const uint8_t* ids, uint32_t q, int64_t now_ns, uint32_t* out_bucket,
+                            void* stream);
+/* The same on host buffers, synchronous. out_bucket is written only when the call succeeds. */
+int kad_table_touch_buckets_host(kad_table* t, const uint8_t* ids, uint32_t q, int64_t now_ns, uint32_t* out_bucket);
+
+/* One read-only pass over the bucket times and the bucket directory: the buckets b >= first_bucket that pass
+ * bucketMaintenance's test (:2833), time[b] < now_ns - 10 min || the bucket has no nodes, ascending, each as one
+ * kad_maint_rec. The caller runs the reference's loop body (randomId, the two rand_trial draws, randomNode) over these
+ * buckets only. `kind` holds
+ *   KAD_MAINT_STALE       the time test holds (strict: time == now - 10 min is not stale, INT64_MIN always is)
+ *   KAD_MAINT_EMPTY       the bucket has no nodes
+ *   KAD_MAINT_HAS_NEXT    std::next(b) != end();  KAD_MAINT_NEXT_EMPTY  ... and it has no nodes
+ *   KAD_MAINT_HAS_PREV    b != begin();           KAD_MAINT_PREV_EMPTY  ... and std::prev(b) has no nodes
+ *   bits 6-7              KAD_MAINT_NEVER / MAYBE / SURE: q->randomNode() of :2838-2850 is non-null for no / some /
+ *                         every outcome of the two rand_trial draws. NEVER buckets are listed too: the reference
+ *                         still draws randomId's bytes for them
+ *   bits 8-15             RoutingTable::randomId's `bit` (routing_table.cpp:30-32), 0..160
+ * totals counts from first_bucket on and holds the true counts whatever cap is; out holds the first `cap` records and
+ * nothing is written at or beyond cap. Deterministic bytes. A caller resumes with first_bucket = last bucket + 1.
+ * Device pointers (totals 4-byte, out 8-byte aligned); enqueues on `stream` and does not synchronise. A const query
+ * whose partial counts live in a stream-ordered allocation of the call's own: concurrent calls on one table on
+ * distinct streams are safe. n_buckets == 0 gives zero totals. Checked in this order, before any device work: NULL
+ * table, NULL totals, a NULL out with a non-zero cap, now_ns < INT64_MIN + 10 min, first_bucket > n_buckets (all
+ * KAD_ERR_INVALID). */
+#define KAD_MAINT_STALE 0x01u
+#define KAD_MAINT_EMPTY 0x02u
+#define KAD_MAINT_HAS_NEXT 0x04u
+#define KAD_MAINT_NEXT_EMPTY 0x08u
+#define KAD_MAINT_HAS_PREV 0x10u
+#define KAD_MAINT_PREV_EMPTY 0x20u
+#define KAD_MAINT_CLASS_SHIFT 6u
+#define KAD_MAINT_NEVER 0u
+#define KAD_MAINT_MAYBE 1u
+#define KAD_MAINT_SURE 2u
+#define KAD_MAINT_BIT_SHIFT 8u
+#define KAD_MAINT_STALE_NS 600000000000ll   /* the 10 minutes of :2833 */
+typedef struct kad_maint_rec {
+    uint32_t bucket;
+    uint32_t kind;
+} kad_maint_rec;
+typedef struct kad_maint_totals {
+    uint32_t candidates;      /* buckets listed (were cap large enough)             */
+    uint32_t stale;           /* ... with KAD_MAINT_STALE                            */
+    uint32_t empty;           /* ... with KAD_MAINT_EMPTY                            */
+    uint32_t sure;            /* ... of class SURE                                   */
+    uint32_t maybe;
+    uint32_t never;
+    uint32_t first_sure;      /* the smallest listed bucket of class SURE, or 0xFFFFFFFF */
+    uint32_t reserved;        /* 0 */
+} kad_maint_totals;
+int kad_table_maintenance(const kad_table* t, int64_t now_ns, uint32_t first_bucket, kad_maint_totals* totals,
+                          kad_maint_rec* out, uint32_t cap, void* stream);
+/* kad_table_maintenance on host buffers, synchronous, ordered after every change made to the table before the call.
+ * The outputs are written only when the call succeeds. */
+int kad_table_maintenance_host(const kad_table* t, int64_t now_ns, uint32_t first_bucket, kad_maint_totals* totals,
+                               kad_maint_rec* out, uint32_t cap);
+/* The same scan on host arrays, without a GPU and without a table (the twin the device pass is tested against; it
+ * shares the kind decision with the kernels): off B + 1 node offsets, first B x 20 bytes, time_ns B entries or NULL
+ * (every bucket at INT64_MIN). The same checks in the same order (NULL off or first with B > 0 in place of the NULL
+ * table), the same record bytes. Sets no error text. */
+int kad_maint_scan_host(uint32_t B, const uint32_t* off, const uint8_t* first, const int64_t* time_ns, int64_t now_ns,
+                        uint32_t first_bucket, kad_maint_totals* totals, kad_maint_rec* out, uint32_t cap);
 
 /* ---- queries: RoutingTable::findClosestNodes ---------------------------- */
 /* Batched RoutingTable::findClosestNodes(target, now, count) (routing_table.cpp:67-111)

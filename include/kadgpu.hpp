@@ -206,6 +206,30 @@ inline const uint8_t* id_bytes(const T& id) {
     return reinterpret_cast<const uint8_t*>(id.data());
 }
 
+/* Bucket::time (routing_table.h:34) in ns where the bucket type has the member; a table type without it (a caller
+ * that does not use the bucket times) mirrors none. */
+template <class B>
+inline auto bucket_time_ns(const B& b, int) -> decltype(to_ns(b.time)) { return to_ns(b.time); }
+template <class B>
+inline int64_t bucket_time_ns(const B&, long) { return INT64_MIN; }
+template <class B>
+inline auto has_bucket_time(int) -> decltype((void)std::declval<const B&>().time, std::true_type()) { return std::true_type(); }
+template <class B>
+inline std::false_type has_bucket_time(long) { return std::false_type(); }
+
+/* What RoutingTableMirror::bucketMaintenance's loop (dht.cpp:2832-2850) came to: found = a node came out; then bucket =
+ * the index of b, q = the index of the bucket the node was drawn from, id = randomId(b), node = q->randomNode(). The
+ * `want` decision (:2852-2866), the request and the scheduler edit stay with the caller. */
+template <class NodePtrT>
+struct MaintenancePick {
+    using InfoHashT = typename std::decay<decltype(std::declval<const NodePtrT&>()->id)>::type;
+    bool found;
+    uint32_t bucket;
+    uint32_t q;
+    InfoHashT id;
+    NodePtrT node;
+};
+
 /* Device mirror of one RoutingTable (one address family). */
 template <class RoutingTableT>
 class RoutingTableMirror {
@@ -225,9 +249,11 @@ public:
     void snapshot(const RoutingTableT& rt, TimePoint now, int device = 0) {
         std::vector<uint8_t> ids, status, first;
         std::vector<uint32_t> off;
+        std::vector<int64_t> btime;
         nodes_.clear();
         for (const auto& b : rt) {
             off.push_back((uint32_t)nodes_.size());
+            btime.push_back(bucket_time_ns(b, 0));
             first.insert(first.end(), id_bytes(b.first), id_bytes(b.first) + KAD_HASH_LEN);
             for (const auto& n : b.nodes) {
                 nodes_.push_back(n);
@@ -238,6 +264,8 @@ public:
         off.push_back((uint32_t)nodes_.size());
         buckets_ = (uint32_t)(off.size() - 1);
         table_ = DeviceTable(device, ids, status, first, off);
+        if (decltype(has_bucket_time<BucketT>(0))::value && buckets_)  // every Bucket::time, where the table has them
+            check(kad_table_set_bucket_times(table_.get(), btime.data()), "kad_table_set_bucket_times");
         first_.swap(first);
         off_.swap(off);
         reindex();
@@ -404,6 +432,114 @@ public:
         expire_calls_++;
         return out;
     }
+    /* Dht::onReportedAddr's bucket write (dht.cpp:3177-3178) for the replies of one tick: findBucket(id)->time = now
+     * for every ID in one kad_table_touch_buckets_host call (reportedAddr(addr) stays with the caller). The host's own
+     * Bucket::time is not written: the device copy is the one bucketMaintenance reads. Pending ops are flushed first.
+     * A table without buckets throws (the reference dereferences end()). */
+    template <class InfoHashT, class TimePoint>
+    void onReportedAddrBatch(const InfoHashT* ids, size_t q, TimePoint now) {
+        flush(now);
+        if (q == 0 && buckets_) return;
+        std::vector<uint8_t> raw(q * KAD_HASH_LEN);
+        for (size_t i = 0; i < q; i++) std::memcpy(&raw[i * KAD_HASH_LEN], id_bytes(ids[i]), KAD_HASH_LEN);
+        check(kad_table_touch_buckets_host(table_.get(), raw.data(), (uint32_t)q, to_ns(now), nullptr),
+              "kad_table_touch_buckets_host");
+    }
+    template <class InfoHashT, class TimePoint>
+    void onReportedAddrBatch(const std::vector<InfoHashT>& ids, TimePoint now) {
+        onReportedAddrBatch(ids.data(), ids.size(), now);
+    }
+    /* A single reply: findBucket over the host's copy of the bucket directory, then one patched word
+     * (kad_table_patch_bucket_times), as the other single requests stay off the launch path. */
+    template <class InfoHashT, class TimePoint>
+    void onReportedAddr(const InfoHashT& id, TimePoint now) {
+        flush(now);
+        if (buckets_ == 0) throw Error(KAD_ERR_INVALID, "onReportedAddr: the table has no buckets");
+        const uint32_t b = bucket_of(id_bytes(id));
+        const int64_t t = to_ns(now);
+        check(kad_table_patch_bucket_times(table_.get(), 1, &b, &t), "kad_table_patch_bucket_times");
+    }
+    /* Dht::connectivityChanged's `b.time = time_point::min()` for every bucket (dht.cpp:2391). */
+    void resetBucketTimes() {
+        if (table_) check(kad_table_set_bucket_times(table_.get(), nullptr), "kad_table_set_bucket_times");
+    }
+    /* The device's bucket times (kad_table_get_bucket_times), one per bucket. */
+    std::vector<int64_t> bucketTimes() const {
+        std::vector<int64_t> t(buckets_);
+        if (buckets_) check(kad_table_get_bucket_times(table_.get(), t.data()), "kad_table_get_bucket_times");
+        return t;
+    }
+    /* Dht::bucketMaintenance's loop (dht.cpp:2832-2850) without the walk over every bucket: the device lists the buckets
+     * that pass :2833 (kad_table_maintenance_host, kMaintenanceCap records per call, resumed behind the last one), and
+     * the reference's loop body runs over those only, drawing from `rd` what the reference draws, in its order and
+     * with its distributions: randomId's bytes (routing_table.cpp:27-45), the two short-circuited rand_trial(1/8)
+     * draws, randomNode's index (routing_table.cpp:15-25). Stops at the first bucket that yields a node. With the same
+     * `rd` it returns what the reference's loop reaches and leaves `rd` in the same state (the reference draws
+     * randomId and randomNode from routing_table.cpp's own generator and the trials from the Dht's; here all come
+     * from the one `rd`). `rt` is the mirrored table: every reported mutation is flushed first, and the mirror's own
+     * directory and node list stand in for it, so it is not walked. neighbourhoodMaintenance has no scan and stays on
+     * the host. */
+    static constexpr uint32_t kMaintenanceCap = 1024;
+    template <class TimePoint, class Rng>
+    MaintenancePick<NodePtr> bucketMaintenance(RoutingTableT& rt, TimePoint now, Rng& rd, uint32_t cap = kMaintenanceCap) {
+        (void)rt;
+        flush(now);
+        MaintenancePick<NodePtr> out{};
+        out.found = false;
+        out.bucket = out.q = KAD_NO_NODE;
+        if (buckets_ == 0 || cap == 0) return out;
+        std::bernoulli_distribution rand_trial(1. / 8.);
+        std::uniform_int_distribution<uint8_t> rand_byte;
+        std::vector<kad_maint_rec> rec(cap);
+        uint32_t fb = 0;
+        for (;;) {
+            kad_maint_totals tot;
+            check(kad_table_maintenance_host(table_.get(), to_ns(now), fb, &tot, rec.data(), cap),
+                  "kad_table_maintenance_host");
+            maint_calls_++;
+            const uint32_t m = tot.candidates < cap ? tot.candidates : cap;
+            for (uint32_t k = 0; k < m; k++) {
+                const uint32_t b = rec[k].bucket, kind = rec[k].kind;
+                typename MaintenancePick<NodePtr>::InfoHashT id{};
+                uint8_t* o = const_cast<uint8_t*>(id_bytes(id));
+                const uint8_t* f = &first_[(size_t)KAD_HASH_LEN * b];
+                const unsigned bit = (kind >> KAD_MAINT_BIT_SHIFT) & 0xFFu;
+                if (bit >= 8 * KAD_HASH_LEN) {
+                    std::memcpy(o, f, KAD_HASH_LEN);
+                } else {
+                    const unsigned bb = bit / 8;
+                    std::memcpy(o, f, bb);
+                    o[bb] = (uint8_t)(f[bb] & (0xFF00 >> (bit % 8)));
+                    o[bb] = (uint8_t)(o[bb] | (rand_byte(rd) >> (bit % 8)));
+                    for (unsigned i = bb + 1; i < KAD_HASH_LEN; i++) o[i] = rand_byte(rd);
+                }
+                bool q_empty = (kind & KAD_MAINT_EMPTY) != 0;
+                uint32_t q = b;
+                if ((kind & KAD_MAINT_HAS_NEXT) && (q_empty || rand_trial(rd))) {
+                    q = b + 1;
+                    q_empty = (kind & KAD_MAINT_NEXT_EMPTY) != 0;
+                }
+                if ((kind & KAD_MAINT_HAS_PREV) && (q_empty || rand_trial(rd)) && !(kind & KAD_MAINT_PREV_EMPTY)) {
+                    q = b - 1;
+                    q_empty = false;
+                }
+                if (q_empty) continue;  // q->randomNode() is null: the loop goes on
+                std::uniform_int_distribution<unsigned> rand_node(0, off_[q + 1] - off_[q] - 1);
+                const unsigned nn = rand_node(rd);
+                out.found = true;
+                out.bucket = b;
+                out.q = q;
+                out.id = id;
+                out.node = nodes_[off_[q] + nn];
+                return out;
+            }
+            if (tot.candidates <= cap) return out;
+            fb = rec[m - 1].bucket + 1;
+        }
+    }
+    /* Bookkeeping for tests: kad_table_maintenance_host calls made by bucketMaintenance. */
+    size_t maintenanceCalls() const { return maint_calls_; }
+
     /* Bookkeeping for tests: full liveness uploads (syncTimes) and expireBuckets calls that removed nodes. */
     size_t syncTimesCalls() const { return sync_calls_; }
     size_t expireCalls() const { return expire_calls_; }
@@ -579,6 +715,16 @@ private:
         index_.clear();
         for (size_t i = 0; i < nodes_.size(); i++) index_[nodes_[i].get()] = (uint32_t)i;
     }
+    // findBucket (routing_table.cpp:113-127) over the host directory: the last bucket whose first is <= t, the first
+    // if none (buckets_ > 0)
+    uint32_t bucket_of(const uint8_t* t) const {
+        uint32_t lo = 0, hi = buckets_;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) / 2;
+            if (std::memcmp(&first_[(size_t)KAD_HASH_LEN * mid], t, KAD_HASH_LEN) <= 0) lo = mid + 1; else hi = mid;
+        }
+        return lo ? lo - 1 : 0;
+    }
     void op(uint32_t kind, uint32_t a, uint32_t b) {
         ops_.push_back(kind);
         ops_.push_back(a);
@@ -607,7 +753,7 @@ private:
     mutable std::vector<uint32_t> updated_;
     mutable int64_t now_ns_ = INT64_MIN;
     mutable bool refresh_ = false;
-    size_t sync_calls_ = 0, expire_calls_ = 0;
+    size_t sync_calls_ = 0, expire_calls_ = 0, maint_calls_ = 0;
 };
 
 /* Device mirror of one NodeCache family map (node_cache.h:42-50: std::map<InfoHash, weak_ptr<Node>>). */
@@ -1658,6 +1804,25 @@ public:
     }
     /* Dht::expireBuckets(buckets(af)) (dht.cpp:942-956, run for both families by Dht::expire) on the mirror. */
     Expired<NodePtr> expireBuckets(sa_family_t af) { return buckets(af).expireBuckets(clock_()); }
+    /* Dht::onReportedAddr's bucket write for one family's replies, at the mirror's clock
+     * (RoutingTableMirror::onReportedAddrBatch / onReportedAddr). */
+    template <class InfoHashT>
+    void onReportedAddrBatch(sa_family_t af, const std::vector<InfoHashT>& ids) {
+        buckets(af).onReportedAddrBatch(ids, clock_());
+    }
+    template <class InfoHashT>
+    void onReportedAddr(sa_family_t af, const InfoHashT& id) { buckets(af).onReportedAddr(id, clock_()); }
+    /* Dht::connectivityChanged's reset of every Bucket::time, both families (dht.cpp:2388-2392). */
+    void resetBucketTimes() {
+        v4_.resetBucketTimes();
+        v6_.resetBucketTimes();
+    }
+    /* Dht::bucketMaintenance(buckets(af)) up to the node it would query (RoutingTableMirror::bucketMaintenance), at the
+     * mirror's clock. */
+    template <class Rng>
+    MaintenancePick<NodePtr> bucketMaintenance(sa_family_t af, RoutingTableT& rt, Rng& rd) {
+        return buckets(af).bucketMaintenance(rt, clock_(), rd);
+    }
     /* Dht::trySearchInsert's verdicts for the candidates of one family (SearchesMirror::trySearchInsertBatch), after
      * snapshotSearches; syncSearches(af, changed) reports the searches the host's inserts changed. */
     void snapshotSearches(const SearchMapT& searches4, const SearchMapT& searches6, int device = 0) {

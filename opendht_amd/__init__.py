@@ -19,6 +19,9 @@ from ._lib import KAD_SR_MARK_MAX_NODES
 from ._lib import (KAD_SR_PLAN_DEFERRED, KAD_SR_PLAN_READY, KAD_SR_PLAN_SKIPPED, KAD_SR_TICK_APPLIED, KAD_SR_TICK_LEFT,
                    KAD_SR_TICK_SKIPPED)
 from ._lib import KAD_SWEEP_INCOMING
+from ._lib import (KAD_MAINT_BIT_SHIFT, KAD_MAINT_CLASS_SHIFT, KAD_MAINT_EMPTY, KAD_MAINT_HAS_NEXT, KAD_MAINT_HAS_PREV,
+                   KAD_MAINT_MAYBE, KAD_MAINT_NEVER, KAD_MAINT_NEXT_EMPTY, KAD_MAINT_PREV_EMPTY, KAD_MAINT_STALE,
+                   KAD_MAINT_STALE_NS, KAD_MAINT_SURE)
 from ._lib import (KAD_SN_CANDIDATE, KAD_SN_NOGET, KAD_SN_PENDING, KAD_SN_SYNCED, KAD_STEP_APPLY, KAD_STEP_DONE,
                    KAD_STEP_DONE_IF_SYNCED, KAD_STEP_EXHAUSTED, KAD_STEP_EXPIRE, KAD_STEP_NO_EXPIRE, KAD_STEP_NO_SEND,
                    KAD_STEP_SHORT, KAD_STEP_SKIPPED, KAD_STEP_SYNCED)
@@ -28,7 +31,7 @@ from .searches import (DeviceSearches, expire_searches, mark_search_nodes, plan_
                        search_step, search_step_batch, search_step_full, search_step_full_batch, start_searches,
                        step_searches, step_searches_full, try_search_insert, try_search_insert_device,
                        try_search_insert_tick)
-from .table import DeviceTable, nc_closest_dual, rt_closest_dual, rt_responsible_dual
+from .table import DeviceTable, maint_scan_host, nc_closest_dual, rt_closest_dual, rt_responsible_dual
 
 __all__ = [
     "DeviceTable", "InfoHash", "KadError", "KAD_MAX_COUNT", "KAD_NO_NODE", "KAD_SEARCH_NODES",
@@ -49,4 +52,7 @@ __all__ = [
     "KAD_STEP_SHORT", "KAD_STEP_SKIPPED", "KAD_STEP_SYNCED", "search_step", "search_step_batch", "step_searches",
     "KAD_SN_ANNOUNCE_DUE", "KAD_SN_LISTEN_DUE", "KAD_STEP_ANNOUNCE", "KAD_STEP_LISTEN", "KAD_STEP_PROBE_BLOCKS",
     "search_step_full", "search_step_full_batch", "step_searches_full",
+    "KAD_MAINT_BIT_SHIFT", "KAD_MAINT_CLASS_SHIFT", "KAD_MAINT_EMPTY", "KAD_MAINT_HAS_NEXT", "KAD_MAINT_HAS_PREV",
+    "KAD_MAINT_MAYBE", "KAD_MAINT_NEVER", "KAD_MAINT_NEXT_EMPTY", "KAD_MAINT_PREV_EMPTY", "KAD_MAINT_STALE",
+    "KAD_MAINT_STALE_NS", "KAD_MAINT_SURE", "maint_scan_host",
 ]

@@ -53,6 +53,11 @@ KAD_STEP_SKIPPED, KAD_STEP_SHORT, KAD_STEP_SYNCED, KAD_STEP_DONE, KAD_STEP_EXHAU
 KAD_SN_LISTEN_DUE, KAD_SN_ANNOUNCE_DUE = 0x40, 0x80
 KAD_STEP_LISTEN, KAD_STEP_ANNOUNCE, KAD_STEP_PROBE_BLOCKS = 0x10, 0x20, 0x40
 KAD_SWEEP_INCOMING = 1
+(KAD_MAINT_STALE, KAD_MAINT_EMPTY, KAD_MAINT_HAS_NEXT, KAD_MAINT_NEXT_EMPTY, KAD_MAINT_HAS_PREV,
+ KAD_MAINT_PREV_EMPTY) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+KAD_MAINT_CLASS_SHIFT, KAD_MAINT_NEVER, KAD_MAINT_MAYBE, KAD_MAINT_SURE, KAD_MAINT_BIT_SHIFT = 6, 0, 1, 2, 8
+KAD_MAINT_STALE_NS = 600_000_000_000
+INT64_MIN = -(1 << 63)
 
 
 def row_words(count: int) -> int:
@@ -132,6 +137,14 @@ SIGNATURES = {
     "kad_table_export_lines": (C.c_int, [_P, C.c_uint32, _P, _P]),
     "kad_table_sweep": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _P]),
     "kad_table_sweep_host": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32]),
+    "kad_table_set_bucket_times": (C.c_int, [_P, _P]),
+    "kad_table_patch_bucket_times": (C.c_int, [_P, C.c_uint32, _P, _P]),
+    "kad_table_get_bucket_times": (C.c_int, [_P, _P]),
+    "kad_table_touch_buckets": (C.c_int, [_P, _P, C.c_uint32, C.c_int64, _P, _P]),
+    "kad_table_touch_buckets_host": (C.c_int, [_P, _P, C.c_uint32, C.c_int64, _P]),
+    "kad_table_maintenance": (C.c_int, [_P, C.c_int64, C.c_uint32, _P, _P, C.c_uint32, _P]),
+    "kad_table_maintenance_host": (C.c_int, [_P, C.c_int64, C.c_uint32, _P, _P, C.c_uint32]),
+    "kad_maint_scan_host": (C.c_int, [C.c_uint32, _P, _P, _P, C.c_int64, C.c_uint32, _P, _P, C.c_uint32]),
     "kad_table_expire": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
     "kad_nc_apply": (C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P]),
     "kad_table_set_times": (C.c_int, [_P, _P, _P, _P]),
@@ -280,6 +293,15 @@ class sweep_totals(C.Structure):
     """kad_sweep_totals"""
     _fields_ = [(n, C.c_uint32) for n in ("good", "dubious", "expired", "incoming", "changed_buckets", "empty_buckets",
                                           "flags", "reserved")]
+
+
+class maint_totals(C.Structure):
+    """kad_maint_totals"""
+    _fields_ = [(n, C.c_uint32) for n in ("candidates", "stale", "empty", "sure", "maybe", "never", "first_sure",
+                                          "reserved")]
+
+
+MAINT_REC_DTYPE = [("bucket", "<u4"), ("kind", "<u4")]  # kad_maint_rec as a numpy record
 
 
 class sr_tick_stats(C.Structure):

@@ -8138,11 +8138,14 @@ struct kad_table {
     hipStream_t bs = nullptr;       // line-set builds (ensure_lines): a non-blocking stream of the table's own
     uint32_t* exp_pin = nullptr;    // pinned read-back of kad_table_expire's lists (grown on demand, kept)
     size_t exp_pin_words = 0;
+    int64_t* btime = nullptr;       // B: Bucket::time in ns, INT64_MIN = time_point::min() (kad_maint.h; NULL: never set)
+    hipEvent_t bt_ev = nullptr;     // recorded after the last kad_table_touch_buckets (the host forms wait on it)
+    bool bt_async = false;
     ~kad_table() {
         if (bs) { (void)hipStreamSynchronize(bs); (void)hipStreamDestroy(bs); }
         for (hipStream_t x : ss)
             if (x) { (void)hipStreamSynchronize(x); (void)hipStreamDestroy(x); }
-        for (hipEvent_t e : {ev_fork, ev_join[0], ev_join[1], mut_ev})
+        for (hipEvent_t e : {ev_fork, ev_join[0], ev_join[1], mut_ev, bt_ev})
             if (e) (void)hipEventDestroy(e);
         delete pipe;
         for (void* p : owned) (void)hipFree(p);
@@ -10914,6 +10917,10 @@ __global__ void mirror_carry_kernel(const uint32_t* __restrict__ remap, uint32_t
         for (uint32_t x = 0; x < rec_words; x++) wrec1[(size_t)rec_words * j + x] = wrec0[(size_t)rec_words * i + x];
 }
 
+// The bucket times of a table whose bucket list a split changed (kad_maint.h).
+int btime_carry_split(const kad_table* t, const uint8_t* first0, uint32_t B0, const uint8_t* first1, uint32_t B1,
+                      int64_t** out, std::vector<void*>& fresh, uint64_t& freshb, std::vector<void*>& tmp, uint64_t& tmpb);
+
 // kad_table_apply; carry (kad_table_expire, removals only): the node times and wire records move with their nodes
 // instead of being dropped.
 // removals (with carry): n_ops old node indices plus rm_base, strictly ascending, in place of op rows.
@@ -11006,6 +11013,11 @@ int table_apply(kad_table* t, const uint32_t* ops, uint32_t n_ops, const uint8_t
         if (hipMemset(wrec1, 0, 4ull * ((size_t)rec_words * n1 + 4)) != hipSuccess)
             return fail(set_err(KAD_ERR_HIP, "hipMemset failed"));
     }
+    // bucket times (kad_table_set_bucket_times): a split's new bucket takes its source bucket's (routing_table.cpp:149)
+    int64_t* btime1 = nullptr;
+    if (t->btime && B1 != B0 &&
+        (rc = btime_carry_split(t, first0, B0, plan.first1.data(), B1, &btime1, fresh, freshb, tmp, tmpb)))
+        return fail(rc);
     if ((rc = dev_upload(&key1, nullptr, n1 + KEY_PAD, fresh, freshb)) ||
         (rc = dev_upload(&tail1, nullptr, 3ull * n1, fresh, freshb)) ||
         (rc = dev_upload(&st1, nullptr, n1, fresh, freshb)))
@@ -11083,6 +11095,7 @@ int table_apply(kad_table* t, const uint32_t* ops, uint32_t n_ops, const uint8_t
     release(t, t->time_ns); release(t, t->reply_ns); release(t, t->expired);
     t->time_ns = time1; t->reply_ns = reply1; t->expired = exp1;
     t->dl.invalidate();
+    if (btime1) { release(t, t->btime); t->btime = btime1; }
     t->h_off.swap(off1);
     if (reshape) t->h_first.swap(first1);
     t->firsts_low_zero = t->firsts_low_zero_next;
@@ -11133,6 +11146,7 @@ int table_apply(kad_table* t, const uint32_t* ops, uint32_t n_ops, const uint8_t
 }  // namespace
 
 #include "kad_sweep.h"
+#include "kad_maint.h"
 
 extern "C" {
 

@@ -236,6 +236,88 @@ class DeviceTable:
                 "expired_nodes": nodes[:min(totals["expired"], cn)] if want_nodes else None,
                 "changed_buckets": buckets[:min(totals["changed_buckets"], cb)] if want_buckets else None}
 
+    # -- bucket times and Dht::bucketMaintenance's scan -----------------------------------------
+    def set_bucket_times(self, time_ns=None) -> None:
+        """Upload every Bucket::time (kad_table_set_bucket_times): (B,) int64 ns, INT64_MIN for time_point::min();
+        None sets every bucket to INT64_MIN."""
+        if time_ns is None:
+            check(lib().kad_table_set_bucket_times(self._h, None), "kad_table_set_bucket_times")
+            return
+        a = np.ascontiguousarray(time_ns, dtype=np.int64)
+        if a.shape != (self.B,):
+            raise ValueError("one time per bucket")
+        check(lib().kad_table_set_bucket_times(self._h, ptr(a)), "kad_table_set_bucket_times")
+
+    def patch_bucket_times(self, buckets, time_ns) -> None:
+        """buckets[j] gets time_ns[j] (kad_table_patch_bucket_times); the later entry of a bucket listed twice wins."""
+        b = np.ascontiguousarray(buckets, dtype=np.uint32)
+        a = np.ascontiguousarray(time_ns, dtype=np.int64)
+        if b.shape != a.shape or b.ndim != 1:
+            raise ValueError("buckets and time_ns must be lists of the same length")
+        check(lib().kad_table_patch_bucket_times(self._h, b.shape[0], ptr(b), ptr(a)), "kad_table_patch_bucket_times")
+
+    def bucket_times(self) -> np.ndarray:
+        """The bucket times as a host (B,) int64 array (kad_table_get_bucket_times)."""
+        out = np.zeros(max(self.B, 1), np.int64)
+        check(lib().kad_table_get_bucket_times(self._h, ptr(out)), "kad_table_get_bucket_times")
+        return out[:self.B]
+
+    def touch_buckets(self, ids, now_ns: int, want_bucket: bool = True, stream=None):
+        """Dht::onReportedAddr per ID (kad_table_touch_buckets): findBucket(id)->time = now_ns. ids: a (q, 20) uint8
+        device tensor (enqueued on the stream; returns the int32 device tensor of buckets, or None), or host IDs
+        (synchronous, kad_table_touch_buckets_host; returns a uint32 array, or None)."""
+        import torch
+
+        if torch.is_tensor(ids):
+            q = ids.shape[0]
+            out = torch.empty((q,), dtype=torch.int32, device=ids.device) if want_bucket else None
+            check(lib().kad_table_touch_buckets(self._h, ptr(ids), q, C.c_int64(now_ns), ptr(out),
+                                                _stream_of(self, stream)), "kad_table_touch_buckets")
+            return out
+        t = _as_ids(ids)
+        out = np.empty((t.shape[0],), dtype=np.uint32) if want_bucket else None
+        check(lib().kad_table_touch_buckets_host(self._h, ptr(t), t.shape[0], C.c_int64(now_ns), ptr(out)),
+              "kad_table_touch_buckets_host")
+        return out
+
+    def maintenance(self, now_ns: int, first_bucket: int = 0, cap=None, stream=None, out=None):
+        """Dht::bucketMaintenance's scan (kad_table_maintenance): {"totals": the kad_maint_totals fields as ints,
+        "records": a (min(candidates, cap), 2) int32 device tensor of (bucket, kind) rows}. cap defaults to the
+        buckets from first_bucket on. out: an int32 device tensor of at least cap rows to write into. Waits for the
+        stream to read the totals."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        s = _stream_of(self, stream)
+        cap = max(self.B - int(first_bucket), 0) if cap is None else int(cap)
+        if out is None and cap:
+            out = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+        tot = torch.empty((8,), dtype=torch.int32, device=dev)
+        check(lib().kad_table_maintenance(self._h, C.c_int64(now_ns), int(first_bucket), ptr(tot),
+                                          ptr(out) if cap else None, cap, s), "kad_table_maintenance")
+        if stream is None:
+            torch.cuda.current_stream(dev).synchronize()
+        elif hasattr(stream, "synchronize"):
+            stream.synchronize()
+        else:
+            torch.cuda.ExternalStream(int(stream), device=dev).synchronize()
+        vals = tot.cpu().numpy().view(np.uint32)
+        totals = {f: int(vals[k]) for k, (f, _) in enumerate(_lib.maint_totals._fields_)}
+        m = min(totals["candidates"], cap)
+        return {"totals": totals,
+                "records": out[:m] if cap else torch.empty((0, 2), dtype=torch.int32, device=dev)}
+
+    def maintenance_host(self, now_ns: int, first_bucket: int = 0, cap=None):
+        """maintenance on host buffers, synchronous (kad_table_maintenance_host): records as a numpy record array
+        (MAINT_REC_DTYPE)."""
+        cap = max(self.B - int(first_bucket), 0) if cap is None else int(cap)
+        rec = np.zeros(max(cap, 1), _lib.MAINT_REC_DTYPE)
+        tot = _lib.maint_totals()
+        check(lib().kad_table_maintenance_host(self._h, C.c_int64(now_ns), int(first_bucket), C.byref(tot),
+                                               ptr(rec) if cap else None, cap), "kad_table_maintenance_host")
+        totals = {f: int(getattr(tot, f)) for f, _ in tot._fields_}
+        return {"totals": totals, "records": rec[:min(totals["candidates"], cap)]}
+
     def expire(self, remap=None):
         """Dht::expireBuckets on the device copy (kad_table_expire): every KAD_STATUS_EXPIRED node leaves; node times
         and wire records stay attached to the survivors. `remap` (device int32 tensor or host uint32 array, old n)
@@ -431,6 +513,29 @@ class DeviceTable:
         check(lib().kad_nc_closest_batch_host(self._h, ptr(t), q, count, ptr(idx), ptr(cnt)),
               "kad_nc_closest_batch_host")
         return idx, cnt
+
+
+def maint_scan_host(bucket_offset, bucket_first, time_ns, now_ns: int, first_bucket: int = 0, cap=None):
+    """Dht::bucketMaintenance's scan over host arrays, without a GPU (kad_maint_scan_host, the twin of
+    DeviceTable.maintenance): bucket_offset (B+1,) uint32, bucket_first (B, 20) uint8, time_ns (B,) int64 or None (every
+    bucket at INT64_MIN). The same dict as DeviceTable.maintenance_host."""
+    off = np.ascontiguousarray(bucket_offset, dtype=np.uint32)
+    B = off.shape[0] - 1
+    first = _as_ids(bucket_first) if B else np.zeros((0, 20), np.uint8)
+    if first.shape[0] != B:
+        raise ValueError("bucket_offset must have B+1 entries")
+    tm = None if time_ns is None else np.ascontiguousarray(time_ns, dtype=np.int64)
+    if tm is not None and tm.shape != (B,):
+        raise ValueError("one time per bucket")
+    cap = max(B - int(first_bucket), 0) if cap is None else int(cap)
+    rec = np.zeros(max(cap, 1), _lib.MAINT_REC_DTYPE)
+    tot = _lib.maint_totals()
+    rc = lib().kad_maint_scan_host(B, ptr(off), ptr(first), ptr(tm), C.c_int64(now_ns), int(first_bucket),
+                                   C.byref(tot), ptr(rec) if cap else None, cap)
+    if rc != 0:
+        raise _lib.KadError(rc, "kad_maint_scan_host", "bad argument")
+    totals = {f: int(getattr(tot, f)) for f, _ in tot._fields_}
+    return {"totals": totals, "records": rec[:min(totals["candidates"], cap)]}
 
 
 def rt_closest_dual(table4: DeviceTable | None, table6: DeviceTable | None, targets, af, count: int,
